@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — tracklet frames/sec of PTT's per-frame hot path on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload car|ped|stress|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload car|ped|stress|train] [--full] [--dump-outputs DIR]
 
 A *step* = one pass of the hot path (ptt_amd.hot_path.FrameHotPath, eval mode) over one batch of synthetic frames
 already resident in HBM. Workloads (BASELINE.json `configs`):
@@ -18,7 +18,11 @@ Launch: under `python -m torch.distributed.run ...` (WORLD_SIZE set) each proces
 and --gpus N > 1 this script re-executes ITSELF under torch.distributed.run with N ranks on 127.0.0.1 (what
 scripts/train_ddp.sh:9 does for the reference's tools/train_tracking.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with, besides the contract keys:
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when --dump-outputs is given
+(DIR/<name>.npy, float32 / float64, at most 64 MB in all: a fixed, seeded sample of larger outputs) and prints ONE JSON
+line on rank 0 (the contract keys first). With --full it also takes every secondary measurement below (each in
+runs of its own after the timed steps) and, for the default car line, the ped / stress / train side workloads
+(`workloads` object) and, at N > 1, the follow-up DDP training launch:
   roofline     the dominant kernel (pt_attn_pair_kernel, fp32 MFMA): algorithmic FLOPs per launch
                / mean launch duration measured live with HIP events on the launch stream, against the 157.3 TFLOP/s
                dense fp32-MFMA peak. `traffic` is null: HBM bytes need rocprofv3 --pmc passes, which this process
@@ -95,10 +99,17 @@ def parse_args():
                     help="N > 1 car line: do not follow it with the training launch (set by bench.py itself when it spawned the ranks: it "
                          "runs that launch from the parent)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="train: only the warm-up and the timed steps (no host-issue measurement, no 8-frame run): the form to put under a profiler")
+                    help="train with --full: no host-issue measurement, no 8-frame run (a plain run takes neither)")
     ap.add_argument("--force-collective", action="store_true",
                     help="take the multi-rank branches (RCCL process group, ranks-seen all-reduce, DistributedDataParallel, the "
                          "no_sync() exposure measurement) at ANY world size, 1 included: how a one-GPU box runs the code an 8-GPU launch runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, take every secondary measurement as well (roofline and per-kernel times, sustained "
+                         "clocks, full model, B = 1 latency and tracklet loop, CPU baseline, training host issue / 8-frame run / "
+                         "all-reduce exposure) and carry the side workloads; off: warm-up, timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy, float32 or "
+                         "float64, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -153,7 +164,8 @@ def launch_ranks(n, extra, capture, timeout=None):
 def train_launch(n):
     """The DDP step of configs[3] on n ranks of their own -> the `workloads.train` record (an `error` record if the launch fails:
     it must not take the headline line down)."""
-    flags = ["--gpus", str(n), "--workload", "train", "--steps", "10", "--warmup", "5", "--sustain", "0", "--no-cpu-baseline", "--no-workloads"]
+    flags = ["--gpus", str(n), "--workload", "train", "--steps", "10", "--warmup", "5", "--sustain", "0", "--no-cpu-baseline", "--no-workloads",
+             "--full"]
     # bounded: this is the first place a run with several RCCL ranks can hang, and the caller still has its own line to print
     rc, train = launch_ranks(n, flags + (["--force-collective"] if n == 1 else []), True, timeout=TRAIN_LAUNCH_TIMEOUT_S)
     if train is not None and rc == 0:
@@ -162,13 +174,13 @@ def train_launch(n):
 
 
 def wants_train_launch(args):
-    return (args.workload == "car" and not args.no_workloads and "train" in args.workloads.split(",") and args.batch is None
+    return (args.full and args.workload == "car" and not args.no_workloads and "train" in args.workloads.split(",") and args.batch is None
             and args.ns is None and args.nt is None and not args.serial and not args.no_graph)
 
 
 def spawn_ranks(n):
     """WORLD_SIZE unset and --gpus n > 1: run this very command line as n ranks under torch.distributed.run — and, for the
-    default car line, run the n ranks a SECOND time on `--workload train` (BASELINE.json configs[3]: the DDP step whose
+    car line with --full, run the n ranks a SECOND time on `--workload train` (BASELINE.json configs[3]: the DDP step whose
     gradient all-reduce over RCCL / xGMI is the only collective of the whole path, tools/train_tracking.py:158-159,
     scripts/train_ddp.sh:9) and carry that line as `workloads.train` of the one JSON line printed: the car workload
     shards frames with no data-path collective, so without the second launch the one command a driver runs at N > 1 would
@@ -270,6 +282,48 @@ def timed_loop(step, steps, sync_all):
         step()
     sync_all()
     return time.perf_counter() - t0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(outputs, prefix=""):
+    """The tensors of a step's result (a tensor, or dicts / tuples of them, nested) -> {name: numpy array}. Floating arrays
+    are written as float32 (float64 stays float64), integer and boolean ones (indices) as float64, which holds them exactly."""
+    import torch
+    arrays = {}
+    if isinstance(outputs, dict):
+        for k, v in outputs.items():
+            arrays.update(output_arrays(v, prefix + str(k) + "."))
+    elif isinstance(outputs, (list, tuple)):
+        for i, v in enumerate(outputs):
+            arrays.update(output_arrays(v, prefix + str(i) + "."))
+    elif isinstance(outputs, torch.Tensor):
+        a = outputs.detach().cpu().numpy()
+        arrays[prefix[:-1]] = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+    return arrays
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: array} -> directory/<name>.npy, at most `limit` bytes in all. The budget is shared smallest array first; an array
+    larger than its share is replaced by a fixed, seeded sample of its elements (flattened, positions in ascending order), so
+    that two builds given the same arguments can be compared output for output. -> {name: "full" | "sample of k of n"}."""
+    os.makedirs(directory, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    written, left = {}, limit - 256 * len(names)                 # room for each file's .npy header
+    for i, name in enumerate(names):
+        a = arrays[name]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            k = max(1, share // a.itemsize)
+            pos = np.sort(np.random.RandomState(0).choice(a.size, k, replace=False))
+            written[name] = "sample of %d of %d elements" % (k, a.size)
+            a = a.reshape(-1)[pos]
+        else:
+            written[name] = "full"
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+    return written
 
 
 def cpu_baseline(model, cfg, s_np, t_np, frames, ns, nt):
@@ -387,9 +441,9 @@ def main():
                            "serialised": graph_policy.graph_mode() == "safe" or (graph_policy.graph_mode() == "auto" and graph_policy._warned)}
     out["cpu_affinity"] = ({"cores_per_rank": len(bound["cores"]), "rank0_cores": bound["cores"][:16], "numa_node": bound["numa_node"],
                             "allowed": bound["allowed"]} if bound else {"bound": False, "allowed": len(os.sched_getaffinity(0))})
-    # BASELINE.json configs[2], [4], [3] beside the headline: the default `python bench.py` line carries a short run of each
-    # (value, ms_per_step, dominant-kernel roofline), so that one driver invocation observes every GPU config
-    if (args.workload == "car" and world == 1 and not args.no_workloads and not args.serial and not args.no_graph
+    # BASELINE.json configs[2], [4], [3] beside the headline: the `python bench.py --full` line carries a short run of each
+    # (value, ms_per_step, dominant-kernel roofline), so that one invocation observes every GPU config
+    if (args.full and args.workload == "car" and world == 1 and not args.no_workloads and not args.serial and not args.no_graph
             and args.batch is None and args.ns is None and args.nt is None):
         out["workloads"] = {}
         for name, steps, warm in (("ped", 20, 5), ("stress", 8, 3), ("train", 20, 5)):
@@ -402,8 +456,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     # N > 1 started by a launcher (`python -m torch.distributed.run ... bench.py --gpus N`, what a driver runs): the car workload
-    # shards frames with no data-path collective, so this command would never meet RCCL beyond a barrier. Once every rank is
-    # through, rank 0 runs the n ranks a second time — on `--workload train`, BASELINE.json configs[3], whose gradient all-reduce
+    # shards frames with no data-path collective, so this command would never meet RCCL beyond a barrier. With --full, once every
+    # rank is through, rank 0 runs the n ranks a second time — on `--workload train`, BASELINE.json configs[3], whose gradient all-reduce
     # over RCCL / xGMI is the only collective of the whole path (tools/train_tracking.py:158-159, scripts/train_ddp.sh:9) — and
     # carries that line as workloads.train. In ranks of their own: the graphs and pools of the car run stay out of its way.
     follow = (world > 1 or os.environ.get("PTT_BENCH_TRAIN_AFTER") == "1") and "WORLD_SIZE" in os.environ and wants_train_launch(args) \
@@ -456,7 +510,7 @@ def side_workload(name, steps, warmup):
     crashes inside hipGraphLaunch on ROCm 7.2 when two parallel branches of a graph are given the same hardware queue — DESIGN.md
     section 6, scripts/probes/graph_queue_repro.py; GPU_MAX_HW_QUEUES=8 avoids it at the price of slower graph replays.)"""
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", str(warmup),
-           "--sustain", "0", "--no-cpu-baseline", "--no-full-model", "--no-latency", "--no-workloads"]
+           "--sustain", "0", "--no-cpu-baseline", "--no-full-model", "--no-latency", "--no-workloads", "--full"]
     t0 = time.perf_counter()
     try:
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -544,17 +598,48 @@ def run_infer(args, torch, ops, dev, dist, world, rank, ranks_seen, sync_all, B,
         graphed = (PipelinedHotPath if pipelined else GraphedHotPath)(model, search, template)
     # pipelined: replay k runs the dense stage of batch k and the sampling stage of batch k+1; K replays
     # therefore execute K full batches' worth of every kernel (the warm-up replays prime the pipeline)
-    step = eager_step if graphed is None else (lambda: graphed())
+    last = {}
+
+    def step():                                 # the step's result is what --dump-outputs writes
+        last["out"] = eager_step() if graphed is None else graphed()
 
     for _ in range(args.warmup):
         step()
     timed = ["ptt_pt_attn_pair_f32", "ptt_fps_f32", "ptt_ball_query_f32", "ptt_sa_fused_fwd_f32", "ptt_linear_f32",
              "ptt_knn_f32"]
-    if graphed is None:
+    event_timed = graphed is None and args.full
+    if event_timed:
         ops.start_kernel_timing(timed)          # HIP events around each launch, inside the timed region
     elapsed = timed_loop(step, args.steps, sync_all)
-    ktimes = ops.stop_kernel_timing() if graphed is None else None
+    ktimes = ops.stop_kernel_timing() if event_timed else None
     elapsed = reduce_max(torch, dist, dev, elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, output_arrays(last["out"]))
+
+    frames_total = float(B) * world * args.steps
+    value = frames_total / elapsed
+    ms_per_step = elapsed / args.steps * 1e3
+    out = {
+        "metric": "tracklet frames/sec (hot path: PointNet++ SA stack + Point-Track-Transformer blocks)",
+        "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%s (%s): batch %d per GPU, %d search + %d template points, SA centres %s / %s, eval"
+                               % (args.workload, W["ref"], B, NS, NT, W["npoints_s"], W["npoints_t"]),
+                   "sample_detail": "%s; 3 SA levels x 2 branches + vote-aggregation SA + 2 TransformerBlocks (d_model 512, k 16), "
+                                    "random-init weights" % W["text"],
+                   "name": args.workload, "frames_per_gpu_per_step": B, "search_points": NS, "template_points": NT,
+                   "sharding": "frames across ranks, no collective",
+                   "launch": ("eager, one stream" if args.serial else "eager" if graphed is None else
+                              "hipGraph replay, template branch on a second stream" +
+                              ("; software-pipelined across batches: FPS of batch n+1 runs on a side stream during the "
+                               "dense kernels of batch n (every batch still executes every kernel)" +
+                               ("; %d such pipelines on their own streams replayed round-robin (%d independent batches in "
+                                "flight)" % (args.ways_used, args.ways_used) if args.ways_used > 1 else "") if pipelined else ""))},
+        "rccl_ranks_seen": ranks_seen,
+    }
+    if not args.full:
+        return out
 
     # ---- the same step at sustained clocks: replay for >= --sustain seconds right after the timed region ----
     sustained = None
@@ -577,10 +662,6 @@ def run_infer(args, torch, ops, dev, dist, world, rank, ranks_seen, sync_all, B,
             eager_step()
         ktimes = ops.stop_kernel_timing()
         model.overlap_branches = True
-
-    frames_total = float(B) * world * args.steps
-    value = frames_total / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
 
     # ---- roofline of the dominant kernel (rank 0's launches) ----
     n_seeds = W["npoints_s"][-1]
@@ -673,24 +754,7 @@ def run_infer(args, torch, ops, dev, dist, world, rank, ranks_seen, sync_all, B,
     if solo and not args.no_cpu_baseline:
         cpu = cpu_baseline(model, cfg, s_np, t_np, args.cpu_frames if args.workload != "stress" else 1, NS, NT)
 
-    out = {
-        "metric": "tracklet frames/sec (hot path: PointNet++ SA stack + Point-Track-Transformer blocks)",
-        "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%s (%s): batch %d per GPU, %d search + %d template points, SA centres %s / %s, eval"
-                               % (args.workload, W["ref"], B, NS, NT, W["npoints_s"], W["npoints_t"]),
-                   "sample_detail": "%s; 3 SA levels x 2 branches + vote-aggregation SA + 2 TransformerBlocks (d_model 512, k 16), "
-                                    "random-init weights" % W["text"],
-                   "name": args.workload, "frames_per_gpu_per_step": B, "search_points": NS, "template_points": NT,
-                   "sharding": "frames across ranks, no collective",
-                   "launch": ("eager, one stream" if args.serial else "eager" if graphed is None else
-                              "hipGraph replay, template branch on a second stream" +
-                              ("; software-pipelined across batches: FPS of batch n+1 runs on a side stream during the "
-                               "dense kernels of batch n (every batch still executes every kernel)" +
-                               ("; %d such pipelines on their own streams replayed round-robin (%d independent batches in "
-                                "flight)" % (args.ways_used, args.ways_used) if args.ways_used > 1 else "") if pipelined else ""))},
-        "rccl_ranks_seen": ranks_seen,
+    out.update({
         "roofline": roofline,
         "cpu_baseline": cpu,
         "sustained": sustained,
@@ -699,7 +763,7 @@ def run_infer(args, torch, ops, dev, dist, world, rank, ranks_seen, sync_all, B,
         "full_model": full,
         "latency_b1": latency,
         "kernel_ms_per_step": kernel_ms,
-    }
+    })
     if cpu:
         out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)
     return out
@@ -867,8 +931,12 @@ def run_train(args, torch, dev, dist, world, rank, ranks_seen, sync_all, B, NS, 
     for _ in range(args.warmup):
         step()
     elapsed = reduce_max(torch, dist, dev, timed_loop(step, args.steps, sync_all))
+    if args.dump_outputs and rank == 0:
+        # the step's caller receives the loss; the parameters it updated in place are the rest of what it computed
+        dump_outputs(args.dump_outputs, output_arrays({"loss": last["loss"],
+                                                       "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])}))
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         n_sus = max(args.steps, int(args.sustain / max(elapsed / args.steps, 1e-6)) + 1)
         dt = reduce_max(torch, dist, dev, timed_loop(step, n_sus, sync_all))
         sustained = {"steps": n_sus, "seconds": round(dt, 3), "value": round(B * world * n_sus / dt, 2),
@@ -885,9 +953,10 @@ def run_train(args, torch, dev, dist, world, rank, ranks_seen, sync_all, B, NS, 
         dt = time.perf_counter() - t0
         torch.cuda.synchronize()
         return round(dt / n * 1e3, 4)
-    issue_ms = None if args.no_extras else host_issue(step)
+    extras = args.full and not args.no_extras
+    issue_ms = host_issue(step) if extras else None
     small = None
-    if world == 1 and not collective and B > 8 and (NS, NT) == (W["ns"], W["nt"]) and not args.no_extras:
+    if world == 1 and not collective and B > 8 and (NS, NT) == (W["ns"], W["nt"]) and extras:
         # 8 frames per GPU: the step the HOST used to bound (12.4 ms of Python / autograd per step whatever the batch)
         torch.manual_seed(1)
         m8 = build_network(ptt_model_cfg(), 1, StubDataset(training=True)).to(dev).train()
@@ -900,7 +969,7 @@ def run_train(args, torch, dev, dist, world, rank, ranks_seen, sync_all, B, NS, 
                  "host_issue_ms_per_step": host_issue(lambda: t8.step(b8)), "graphs_per_step": 1 if t8.captured is not None else 0}
         del t8, m8
     allreduce = None
-    if collective:
+    if collective and args.full:
         # what the gradient all-reduce costs the step: the same steps with DDP's synchronisation switched off
         # (model.no_sync(): gradients stay local; the replicas drift apart, which is why this runs last)
         def step_local():

@@ -62,7 +62,8 @@ def bench_mode(order, rounds):
                hp=(FrameHotPath, GraphedHotPath, InterleavedHotPath, PipelinedHotPath, TrackerThroughput, kitti_model_cfg, randomize_))
     for rnd in range(rounds):
         for name in order:
-            sys.argv = ["bench.py", "--workload", name, "--steps", "5", "--warmup", "2", "--sustain", "0.3", "--no-cpu-baseline", "--no-workloads"]
+            sys.argv = ["bench.py", "--workload", name, "--steps", "5", "--warmup", "2", "--sustain", "0.3", "--no-cpu-baseline", "--no-workloads",
+                        "--full"]
             if name == "car":
                 sys.argv += os.environ.get("PROBE_CAR_FLAGS", "").split()
             args = bench.parse_args()

@@ -28,11 +28,11 @@ def test_workloads_cover_the_baseline_configs():
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful where no HIP device is visible")
 def test_gpus_2_spawns_two_ranks_itself():
-    """`python bench.py --gpus 2` (what a driver runs at N > 1) launches the 2 ranks TWICE: the car headline, then the DDP
+    """`python bench.py --gpus 2 --full` launches the 2 ranks TWICE: the car headline, then the DDP
     training step of configs[3] whose line rides as workloads.train — on a GPU-less host every rank of both launches stops
     at "needs a HIP device", which is the observable proof that 2 x 2 ranks were started."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode != 0
     spawns = [l for l in p.stderr.splitlines() if "spawn: 2 ranks" in l]
@@ -61,6 +61,57 @@ def test_launched_ranks_get_an_environment_without_the_outer_launchers_variables
     assert "--force-collective" not in seen["cmd"]
     bench.train_launch(1)
     assert "--force-collective" in seen["cmd"]                      # one rank: the collective branches are taken anyway
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful where no HIP device is visible")
+def test_a_plain_gpus_2_run_is_one_launch():
+    """Without --full, `python bench.py --gpus 2` (what a driver runs at N > 1) launches its 2 ranks once, on the car headline
+    alone: no follow-up training launch."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert p.returncode != 0 and "bench.py needs a HIP device" in p.stderr, p.stderr[-2000:]
+    spawns = [l for l in p.stderr.splitlines() if "spawn: 2 ranks" in l]
+    assert len(spawns) == 1 and "--workload train" not in spawns[0], p.stderr[-2000:]
+
+
+def test_full_is_off_by_default_and_gates_the_side_runs(monkeypatch):
+    """A plain command line takes no secondary measurement: --full is off unless given, and only with it does the car line ask for the
+    training launch of N > 1; --dump-outputs names a directory."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    args = bench.parse_args()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 3
+    assert not bench.wants_train_launch(args)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.full is True and args.dump_outputs == "out" and bench.wants_train_launch(args)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: every tensor of a step's result as <name>.npy, floating in float32 (float64 kept), integers in float64 (exact);
+    past the byte budget the largest arrays become a fixed, seeded sample of their elements — the same for the same input."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = {"feats": torch.randn(64, 1000, generator=g), "inds": torch.arange(300, dtype=torch.int32).view(3, 100),
+           "nested": (torch.ones(5, dtype=torch.float64), torch.zeros(2, dtype=torch.float16)), "not_a_tensor": 3}
+    arrays = bench.output_arrays(out)
+    assert sorted(arrays) == ["feats", "inds", "nested.0", "nested.1"]
+    assert arrays["feats"].dtype == np.float32 and arrays["inds"].dtype == np.float64 and arrays["nested.0"].dtype == np.float64
+    assert arrays["nested.1"].dtype == np.float32 and np.array_equal(arrays["inds"], np.arange(300).reshape(3, 100))
+    info = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert set(info.values()) == {"full"}
+    assert np.array_equal(np.load(tmp_path / "all" / "feats.npy"), out["feats"].numpy())
+    limit = 16384
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), bench.output_arrays(out), limit=limit)
+    assert info["inds"] == "full" and info["feats"].startswith("sample of ")
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit
+    x = np.load(tmp_path / "a" / "feats.npy")
+    assert np.array_equal(x, np.load(tmp_path / "b" / "feats.npy")) and np.isin(x, out["feats"].numpy()).all()
 
 
 def test_gpus_2_with_another_workload_is_one_launch():
