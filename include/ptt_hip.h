@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 21
+#define PTT_ABI_VERSION 22
 
 enum {
     PTT_OK = 0,
@@ -309,9 +309,24 @@ typedef struct ptt_sa_desc {
     const float* l0_xyz_weight;
     int l0_channels;
     int l0_relu;
+    /* Optional (ABI 22): workspace of at least ptt_sa_compact_workspace(B, M) bytes for the level without point features
+     * (C == 0, use_xyz, nsample 32, 3 -> 64 -> 64 -> 128, the SA0 shape). Non-NULL: two extra launches first reduce every
+     * ball to its DISTINCT rows — a ball's padding slots repeat its first hit, and neighbours with bit-identical (x,y,z)
+     * give bit-identical rows — padded to a class size c in {4, 8, 16, 32}, and the MLP runs on 32 / c balls per 32-row
+     * tile. The max over a multiset equals the max over its distinct members: the output is bitwise the dense one.
+     * Ignored by the other shapes; NULL = every one of the nsample rows (the dense path). idx is not modified.
+     * Layout (int32 words, T = B*M; read by tests, not an interface to build on):
+     *   [0, 4)                 balls per class (c = 4, 8, 16, 32), [4, 16) reserved
+     *   [16, 16+T)             distinct rows per ball
+     *   [16+T+k*T, +T)         the balls (b*M + m) of class k, in any order (first n_k entries)
+     *   [16+5T+(c_k-4)*T, +c_k*T)  their rows: ball at list position q owns entries [q*c_k, (q+1)*c_k) — its distinct
+     *                          neighbour indices in slot order, then the first one repeated */
+    void* compact_ws;
+    size_t compact_ws_bytes;
 } ptt_sa_desc;
 
 int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream);
+size_t ptt_sa_compact_workspace(int B, int M);
 
 /* ---------------------------------------------------------------------------------
  * N1  P2B cosine-similarity feature augmentation, fused

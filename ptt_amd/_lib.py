@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libptt_hip.so")
 
 PTT_SA_MAX_LAYERS = 4
-ABI_VERSION = 21            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
+ABI_VERSION = 22            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
 
 # every symbol include/ptt_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -44,7 +44,7 @@ EXPORTS = [
     "ptt_track_losses_f32", "ptt_track_losses_bwd_f32", "ptt_adam_chunk_elems", "ptt_adam_clip_step_f32", "ptt_adam_clip_step_dev_f32",
     "ptt_linear_wgrad_partials_f32", "ptt_linear_wgrad2_partials_f32", "ptt_colsum_partials_f32", "ptt_grad_finish_f32",
     "ptt_rows_gemm_rsum16_supported", "ptt_rows_gemm_rsum16_f32", "ptt_scatter_rows_csr_sub_f32",
-    "ptt_unit_rows_f32", "ptt_cos_bwd_rows_f32", "ptt_track_select_update", "ptt_sa_z0_bnbwd_workspace", "ptt_sa_z0_bnbwd_f32",
+    "ptt_unit_rows_f32", "ptt_cos_bwd_rows_f32", "ptt_track_select_update", "ptt_sa_z0_bnbwd_workspace", "ptt_sa_compact_workspace", "ptt_sa_z0_bnbwd_f32",
 ]
 PTT_MAX_SEGMENTS = 4
 
@@ -148,7 +148,8 @@ class SaDesc(Structure):
                 ("B", c_int), ("N", c_int), ("M", c_int), ("nsample", c_int), ("C", c_int),
                 ("radius", c_float), ("use_xyz", c_int), ("normalize_xyz", c_int), ("n_layers", c_int),
                 ("layers", SaLayer * PTT_SA_MAX_LAYERS),
-                ("l0_point_term", c_void_p), ("l0_xyz_weight", c_void_p), ("l0_channels", c_int), ("l0_relu", c_int)]
+                ("l0_point_term", c_void_p), ("l0_xyz_weight", c_void_p), ("l0_channels", c_int), ("l0_relu", c_int),
+                ("compact_ws", c_void_p), ("compact_ws_bytes", c_size_t)]
 
 
 class XcorrDesc(Structure):
@@ -302,6 +303,8 @@ def _declare(lib):
     lib.ptt_xcorr_z0_bwd_workspace.argtypes = [i, i, i]
     lib.ptt_sa_z0_bnbwd_workspace.restype = c_size_t
     lib.ptt_sa_z0_bnbwd_workspace.argtypes = [c_longlong, i]
+    lib.ptt_sa_compact_workspace.restype = c_size_t
+    lib.ptt_sa_compact_workspace.argtypes = [i, i]
     lib.ptt_adam_chunk_elems.restype = c_int
     lib.ptt_adam_chunk_elems.argtypes = []
     lib.ptt_colsum_workspace.restype = c_size_t

@@ -545,6 +545,7 @@ struct SaParams {
     const float* wx;
     float radius;
     long long* dbg;   // dev only (PTT_DEBUG_STAMPS)
+    int32_t* cws;     // sa_lds_kernel: the ball table of sa_compact_kernel (ptt_sa_desc.compact_ws), NULL = every grouped row
     SaLayerDev L[PTT_SA_MAX_LAYERS];
 };
 
@@ -1479,6 +1480,93 @@ __device__ __forceinline__ void sa_wave_layer(const SaParams& p, const SaLayerDe
 }
 
 // ------------------------------------------------------------------------------------------
+// SA0 ball compaction (ptt_sa_desc.compact_ws; the table's layout is documented in include/ptt_hip.h). A ball's rows
+// are redundant twice over: ball query fills the slots after the last hit with the first hit, and at SA0 a row is only
+// (x_j - c) / r, so neighbours with bit-identical coordinates (the resampled clouds repeat points) give bit-identical
+// rows. Every row goes through the same layer chain in the same K order and the rows are then max-pooled: pooling the
+// DISTINCT rows alone gives the same bits. One half-wave per ball: slot s is kept when no earlier slot holds the same
+// (x, y, z) bit patterns (integer compares: +0 / -0 and NaN payloads stay apart); the kept indices, in slot order, are
+// padded with the first one to a class size c in {4, 8, 16, 32} and appended to that class's list (one global atomic
+// per class and workgroup). List order depends on the atomics; the pooled outputs do not.
+// ------------------------------------------------------------------------------------------
+constexpr int SAC_HDR = 16;                                  // int32 words ahead of the per-ball arrays
+struct SacTable {
+    int32_t* ws; int T;
+    __host__ __device__ int32_t* ndist() const { return ws + SAC_HDR; }
+    __host__ __device__ int32_t* list(int k) const { return ws + SAC_HDR + (size_t)(1 + k) * T; }
+    __host__ __device__ int32_t* rows(int k) const { return ws + SAC_HDR + 5 * (size_t)T + (size_t)((4 << k) - 4) * T; }
+    static size_t words(size_t T) { return SAC_HDR + 65 * T; }
+};
+constexpr int SAC_PASSES = 4;                                // 4 waves x 2 balls x 4 passes = 32 balls per workgroup
+
+// the class counters start at zero (a kernel node rather than a memset node in a captured step)
+__global__ __launch_bounds__(64) void sa_compact_zero_kernel(int32_t* ws) {
+    if (threadIdx.x < 4) ws[threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(256) void sa_compact_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ idx, int N, int M,
+                                                         SacTable tab) {
+    __shared__ int s_cnt[4], s_base[4], s_cls[32], s_pos[32], s_nd[32];
+    __shared__ int s_row[32][32];
+    const int t = threadIdx.x, lane = t & 63, half = lane >> 5, s = lane & 31, w = t >> 6;
+    const int g0 = blockIdx.x * 32, T = tab.T;
+    if (t < 4) s_cnt[t] = 0;
+    __syncthreads();
+    int iv[SAC_PASSES];
+    uint32_t x[SAC_PASSES], y[SAC_PASSES], z[SAC_PASSES];
+#pragma unroll
+    for (int q = 0; q < SAC_PASSES; ++q) iv[q] = idx[(size_t)min(g0 + q * 8 + w * 2 + half, T - 1) * 32 + s];
+#pragma unroll
+    for (int q = 0; q < SAC_PASSES; ++q) {
+        const int b = min(g0 + q * 8 + w * 2 + half, T - 1) / M;
+        const uint32_t* pt = reinterpret_cast<const uint32_t*>(xyz) + ((size_t)b * N + iv[q]) * 3;
+        x[q] = pt[0]; y[q] = pt[1]; z[q] = pt[2];
+    }
+#pragma unroll
+    for (int q = 0; q < SAC_PASSES; ++q) {
+        const int lc = q * 8 + w * 2 + half;
+        const int i0a = __builtin_amdgcn_readlane(iv[q], 0), i0b = __builtin_amdgcn_readlane(iv[q], 32);
+        const int i0 = half ? i0b : i0a;
+        const bool real = s == 0 || iv[q] != i0;               // a padding slot repeats slot 0
+        const unsigned long long rm = __ballot(real);
+        // the highest real slot of either ball bounds the candidates an earlier slot can duplicate
+        const int J = 31 - __builtin_clz((uint32_t)rm | (uint32_t)(rm >> 32));
+        // both halves' slot j read unconditionally, then selected, and the tests combined bitwise: a readlane under a
+        // per-lane condition or a short-circuit && turns the loop into divergent branches (measured 20-26 us a launch)
+        int dup = 0;
+        for (int j = 0; j < J; ++j) {
+            const uint32_t xa = __builtin_amdgcn_readlane(x[q], j), xb = __builtin_amdgcn_readlane(x[q], 32 + j);
+            const uint32_t ya = __builtin_amdgcn_readlane(y[q], j), yb = __builtin_amdgcn_readlane(y[q], 32 + j);
+            const uint32_t za = __builtin_amdgcn_readlane(z[q], j), zb = __builtin_amdgcn_readlane(z[q], 32 + j);
+            dup |= (int)(j < s) & (int)(x[q] == (half ? xb : xa)) & (int)(y[q] == (half ? yb : ya)) & (int)(z[q] == (half ? zb : za));
+        }
+        const bool keep = real && !dup;
+        const unsigned long long km = __ballot(keep);
+        const uint32_t m = half ? (uint32_t)(km >> 32) : (uint32_t)km;
+        const int nd = __popc(m);                              // >= 1: slot 0 is always kept
+        if (keep) s_row[lc][__popc(m & ((1u << s) - 1u))] = iv[q];
+        if (s == 0) {
+            const int k = nd <= 4 ? 0 : nd <= 8 ? 1 : nd <= 16 ? 2 : 3;
+            const bool valid = g0 + lc < T;
+            s_cls[lc] = valid ? k : -1;
+            s_nd[lc] = nd;
+            s_pos[lc] = valid ? atomicAdd(&s_cnt[k], 1) : 0;
+            if (valid) tab.ndist()[g0 + lc] = nd;
+        }
+    }
+    __syncthreads();
+    if (t < 4) s_base[t] = s_cnt[t] ? atomicAdd(&tab.ws[t], s_cnt[t]) : 0;
+    __syncthreads();
+    for (int e = t; e < 32 * 32; e += 256) {
+        const int lc = e >> 5, j = e & 31, k = s_cls[lc];
+        if (k < 0 || j >= (4 << k)) continue;
+        const int q = s_base[k] + s_pos[lc];
+        tab.rows(k)[(size_t)q * (4 << k) + j] = s_row[lc][j < s_nd[lc] ? j : 0];
+        if (j == 0) tab.list(k)[q] = g0 + lc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // SA0 (no point features: rows are [rel.x rel.y rel.z], 3 -> 64 -> 64 -> 128, 32 neighbours): the activations never
 // leave the registers. A PERSISTENT workgroup of 8 waves per CU holds the packed weights of layers 1 and 2 (48 KB) in
 // LDS; every wave owns whole centres (32 grouped rows x all channels) and chains the layers TRANSPOSED:
@@ -1493,6 +1581,11 @@ __device__ __forceinline__ void sa_wave_layer(const SaParams& p, const SaLayerDe
 // step against the constant (1, 0); layer 2's shift is added after the pool.
 // (The earlier form kept a private [32][68] LDS tile per wave: ~250 epilogue instructions per 200 MFMAs, each paid in
 //  matrix time beside the co-resident wave's MFMA stream — 0.71 of peak.)
+// COMPACT (p.cws != NULL): the tiles are those of sa_compact_kernel's table, classes 4, 8, 16, 32 one after the other;
+// a tile holds 32 / c balls of one class, row s = slot s % c of ball s / c (the partial last tile of a class repeats its
+// first ball's rows; those balls are not stored). Ball g of a tile is accumulator rows [g c, (g + 1) c): 4 registers of
+// one half-wave for c = 4, plus the lane ^ 32 exchange for 8 and 16. Tile j of the launch goes to workgroup j % G,
+// wave (j / G) % waves: every CU gets the same number of tiles within one.
 // ------------------------------------------------------------------------------------------
 #ifndef PTT_SAL_WGS
 #define PTT_SAL_WGS 1        // workgroups per CU
@@ -1500,6 +1593,83 @@ __device__ __forceinline__ void sa_wave_layer(const SaParams& p, const SaLayerDe
 #ifndef PTT_SAL_WAVES
 #define PTT_SAL_WAVES 12     // waves per workgroup (three per SIMD: 148 VGPRs)
 #endif
+
+// the tile `j` of the compact table: class k, first list position, balls in it
+struct SacTile {
+    int k, first, n;
+    __device__ __forceinline__ void at(int j, const int (&tiles)[4], const int (&cnt)[4]) {
+        k = j < tiles[0] ? 0 : j < tiles[1] ? 1 : j < tiles[2] ? 2 : 3;
+        // selects, not indexing: a run-time index would put both arrays in scratch
+        const int j0 = k == 0 ? 0 : k == 1 ? tiles[0] : k == 2 ? tiles[1] : tiles[2];
+        const int nk = k == 0 ? cnt[0] : k == 1 ? cnt[1] : k == 2 ? cnt[2] : cnt[3];
+        first = (j - j0) << (3 - k);                         // 8 >> k balls per tile
+        n = min(8 >> k, nk - first);
+    }
+    // row `s` of the tile: (neighbour index, ball)
+    __device__ __forceinline__ void row(const SacTable& tab, int s, int& n_out, int& ball) const {
+        const int cl = s >> (2 + k), inb = cl < n;
+        n_out = tab.rows(k)[(size_t)first * (4 << k) + (inb ? s : (s & ((4 << k) - 1)))];
+        ball = tab.list(k)[first + (inb ? cl : 0)];
+    }
+};
+
+// compact tile epilogue: the max over each ball's c rows (c = 4 << k), layer 2's shift, ReLU — the same arithmetic as
+// sas_pool on fewer rows — stored for the tile's n balls. Rows of ball g: registers 4q..4q+3 of half-wave g & 1
+// (q = g >> 1) for c = 4; registers 4g..4g+3 of both halves for c = 8; 8g..8g+7 of both halves for c = 16.
+// `ball`: the ball of this lane's row (ball g of the tile is the one of row g c, read from that lane).
+__device__ __forceinline__ void sac_store(const SaParams& p, const SacTile& tc, int ball, const f32x16 (&acc)[4], const float* cst,
+                                          int half, int col, int osb, int osm, int osc) {
+    const int k = tc.k, relu = p.L[2].relu;
+    int ob[8];                                               // output offset of ball g (wave-uniform)
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        if (g >= (8 >> k)) break;
+        const int id = __builtin_amdgcn_readlane(ball, g << (2 + k)), b = id / p.M;
+        ob[g] = b * osb + (id - b * p.M) * osm;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float sh = cst[(6 + u) * 64];
+        float* o = p.out + (u * 32 + col) * osc;
+        const f32x16& a = acc[u];
+        if (k == 3) {
+            const float mx = sas_pool(a, sh, relu);
+            if (half == 0) o[ob[0]] = mx;
+        } else if (k == 2) {
+            float m0 = a[0], m1 = a[8];
+#pragma unroll
+            for (int r = 1; r < 8; ++r) { m0 = fmaxf(m0, a[r]); m1 = fmaxf(m1, a[8 + r]); }
+            m0 = max_halves(m0) + sh; m1 = max_halves(m1) + sh;
+            if (relu) { m0 = fmaxf(m0, 0.f); m1 = fmaxf(m1, 0.f); }
+            if (half < tc.n) o[half ? ob[1] : ob[0]] = half ? m1 : m0;       // half-wave h stores ball h
+        } else {
+            float m[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) m[q] = fmaxf(fmaxf(a[4 * q], a[4 * q + 1]), fmaxf(a[4 * q + 2], a[4 * q + 3]));
+            if (k == 1) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) m[q] = max_halves(m[q]) + sh;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {                // half-wave h stores balls 2h, 2h + 1
+                    const int g = 2 * half + i;
+                    float v = half ? m[2 + i] : m[i];
+                    if (relu) v = fmaxf(v, 0.f);
+                    if (g < tc.n) o[half ? ob[2 + i] : ob[i]] = v;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int g = 2 * q + half;
+                    float v = m[q] + sh;
+                    if (relu) v = fmaxf(v, 0.f);
+                    if (g < tc.n) o[half ? ob[2 * q + 1] : ob[2 * q]] = v;
+                }
+            }
+        }
+    }
+}
+
+template <bool COMPACT>
 __global__ __launch_bounds__(64 * PTT_SAL_WAVES) __attribute__((amdgpu_waves_per_eu(PTT_SAL_WAVES * PTT_SAL_WGS / 4)))
 void sa_lds_kernel(SaParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1507,6 +1677,18 @@ void sa_lds_kernel(SaParams p) {
     float* W2 = smem + 4096;                                 // [8][4][256]   64 x 128
     const int t = threadIdx.x, lane = t & 63, half = lane >> 5, col = lane & 31;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int total = p.B * p.M, M = p.M, N = p.N;
+    const int nw = (int)blockDim.x >> 6;
+    SacTable tab{p.cws, total};
+    int cnt[4], tiles[4];                                    // compact: balls per class, running tile counts
+    if constexpr (COMPACT) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cnt[k] = min(max(p.cws[k], 0), total);
+            tiles[k] = (k ? tiles[k - 1] : 0) + ((cnt[k] + (8 >> k) - 1) >> (3 - k));
+        }
+        if (logical_block() >= tiles[3]) return;             // no tile for this workgroup: skip the weight load
+    }
     {
         const f32x4* g1 = reinterpret_cast<const f32x4*>(p.L[1].Wp);
         const f32x4* g2 = reinterpret_cast<const f32x4*>(p.L[2].Wp);
@@ -1532,9 +1714,14 @@ void sa_lds_kernel(SaParams p) {
     for (int u = 0; u < 4; ++u) cst[(6 + u) * 64] = p.L[2].shift ? p.L[2].shift[u * 32 + col] : 0.f;
     const float one_zero = half ? 0.f : 1.f, one_hi = 1.f;
     __syncthreads();
-    const int total = p.B * p.M, M = p.M, N = p.N;           // one tile per centre
-    const int gw = logical_block() * ((int)blockDim.x >> 6) + w;
-    const int c0 = gw * p.chunk, c1 = min(total, c0 + p.chunk);
+    // the work of this wave: dense = centres [c0, c1), one tile each; compact = tiles lb + G (w + nw i) of the table
+    int c0, c1, cstep;
+    if constexpr (COMPACT) {
+        c0 = logical_block() + (int)gridDim.x * w; c1 = tiles[3]; cstep = (int)gridDim.x * nw;
+    } else {
+        const int gw = logical_block() * nw + w;
+        c0 = gw * p.chunk; c1 = min(total, c0 + p.chunk); cstep = 1;
+    }
     if (c0 >= c1) return;
     const float rdiv = p.normalize ? p.radius : 1.0f;        // x / 1 is exact: one code path
     const int osb = (int)p.osb, osm = (int)p.osm, osc = (int)p.osc;
@@ -1543,12 +1730,21 @@ void sa_lds_kernel(SaParams p) {
     const float* b2p = W2 + lane * 4;
     const __amdgpu_buffer_rsrc_t rx = weight_rsrc(p.xyz);
 
-    SasCentre ce;
-    ce.c = c0; ce.b = c0 / M; ce.m = c0 - ce.b * M;
+    SasCentre ce{0, 0, 0};                                   // dense: the current centre
+    SacTile tc{0, 0, 0};                                     // compact: the current tile
     // every lane: grouped row `col` of the tile (both half-waves hold the same rows and supply different K indices)
-    int n_cur = p.idx[(size_t)c0 * 32 + col];
     float px, py, pz, cx, cy, cz;
-    {
+    int g_cur = 0;                                           // compact: the ball of row `col`
+    if constexpr (COMPACT) {
+        tc.at(c0, tiles, cnt);
+        int n_cur;
+        tc.row(tab, col, n_cur, g_cur);
+        const size_t flat = (size_t)(g_cur / M) * N + n_cur;
+        px = p.xyz[flat * 3]; py = p.xyz[flat * 3 + 1]; pz = p.xyz[flat * 3 + 2];
+        cx = p.new_xyz[(size_t)g_cur * 3]; cy = p.new_xyz[(size_t)g_cur * 3 + 1]; cz = p.new_xyz[(size_t)g_cur * 3 + 2];
+    } else {
+        ce.c = c0; ce.b = c0 / M; ce.m = c0 - ce.b * M;
+        const int n_cur = p.idx[(size_t)c0 * 32 + col];
         const size_t flat = (size_t)ce.b * N + n_cur;
         px = p.xyz[flat * 3]; py = p.xyz[flat * 3 + 1]; pz = p.xyz[flat * 3 + 2];
         cx = p.new_xyz[(size_t)c0 * 3]; cy = p.new_xyz[(size_t)c0 * 3 + 1]; cz = p.new_xyz[(size_t)c0 * 3 + 2];
@@ -1556,10 +1752,17 @@ void sa_lds_kernel(SaParams p) {
     // Loads are pinned where their latency is covered (sched_barrier: left alone, the scheduler sinks the next tile's
     // index load to its first use and waits vmcnt(0) in the middle of layer 2, and issues each weight fragment's
     // ds_read right in front of the MFMAs that consume it)
-    for (int c = c0; c < c1; ++c) {
+    for (int c = c0; c < c1; c += cstep) {
         SasCentre nx = ce;                                   // the last tile re-requests itself (branch-free loop body)
-        if (c + 1 < c1) nx.advance(1, M);
-        const int n_next = p.idx[(size_t)nx.c * 32 + col];   // in flight under layers 0 and 1
+        SacTile tx = tc;
+        int n_next, g_next;
+        if constexpr (COMPACT) {
+            if (c + cstep < c1) tx.at(c + cstep, tiles, cnt);
+            tx.row(tab, col, n_next, g_next);                // in flight under layers 0 and 1
+        } else {
+            if (c + 1 < c1) nx.advance(1, M);
+            n_next = p.idx[(size_t)nx.c * 32 + col];         // in flight under layers 0 and 1
+        }
         f32x4 wa[2], wn[2];                                  // layer 1's weight fragments: current / next K-block
 #pragma unroll
         for (int u = 0; u < 2; ++u) wa[u] = *reinterpret_cast<const f32x4*>(a1p + u * 256);
@@ -1611,11 +1814,12 @@ void sa_lds_kernel(SaParams p) {
         // the next tile's coordinates: in flight under layer 2
         {   // 32-bit offsets on a buffer descriptor: with 64-bit index arithmetic the sign extension of n_next is hoisted
             // to the load and the wave waits vmcnt(0) at the top of the tile
-            const int off = (nx.b * N + n_next) * 12;
+            const int g = COMPACT ? g_next : nx.c;
+            const int off = ((COMPACT ? g_next / M : nx.b) * N + n_next) * 12;
             px = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, off, 0, 0));
             py = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, off + 4, 0, 0));
             pz = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, off + 8, 0, 0));
-            cx = p.new_xyz[(size_t)nx.c * 3]; cy = p.new_xyz[(size_t)nx.c * 3 + 1]; cz = p.new_xyz[(size_t)nx.c * 3 + 2];
+            cx = p.new_xyz[(size_t)g * 3]; cy = p.new_xyz[(size_t)g * 3 + 1]; cz = p.new_xyz[(size_t)g * 3 + 2];
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- layer 2: 64 -> 128 (rows back on the M axis), max over the 32 neighbours, shift, ReLU after the pool ----
@@ -1638,14 +1842,18 @@ void sa_lds_kernel(SaParams p) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) wb[u] = wm[u];
             }
-            float* o = p.out + (ce.b * osb + ce.m * osm);
+            if constexpr (COMPACT) {
+                sac_store(p, tc, g_cur, acc, cst, half, col, osb, osm, osc);
+            } else {
+                float* o = p.out + (ce.b * osb + ce.m * osm);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float mx = sas_pool(acc[u], cst[(6 + u) * 64], p.L[2].relu);
-                if (half == 0) o[(u * 32 + col) * osc] = mx;
+                for (int u = 0; u < 4; ++u) {
+                    const float mx = sas_pool(acc[u], cst[(6 + u) * 64], p.L[2].relu);
+                    if (half == 0) o[(u * 32 + col) * osc] = mx;
+                }
             }
         }
-        ce = nx;
+        if constexpr (COMPACT) { tc = tx; g_cur = g_next; } else ce = nx;
     }
 }
 
@@ -2056,6 +2264,11 @@ extern "C" int ptt_rows_mlp_f32(const float* X, int rows, int K, int ldx, const 
     return check_launch("rows_mlp_kernel");
 }
 
+extern "C" size_t ptt_sa_compact_workspace(int B, int M) {
+    const long long T = (long long)(B > 0 ? B : 0) * (M > 0 ? M : 0);
+    return SacTable::words((size_t)T) * sizeof(int32_t);
+}
+
 extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
     if (!d) return fail(PTT_EINVAL, "ptt_sa_fused_fwd_f32: null descriptor");
     if (d->B < 0 || d->N <= 0 || d->M < 0 || d->C < 0 || d->n_layers < 1 || d->n_layers > PTT_SA_MAX_LAYERS)
@@ -2119,6 +2332,7 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
                     (p.fsb & 3) == 0 && (reinterpret_cast<uintptr_t>(p.feat) & 15) == 0) ? 1 : 0;
     p.first_wave = 1024; p.stagger = dev_switches().sa_stagger;
     p.dbg = dev_switches().stamps;
+    p.cws = nullptr;
     const int total_centres = d->B * d->M;
     hipStream_t s = as_stream(stream);
     int rc;
@@ -2137,8 +2351,26 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
         const int nw = total_centres * 3 <= 256 * PTT_SAL_WAVES ? 4 : PTT_SAL_WAVES;
         int wgs = (total_centres + p.chunk * nw - 1) / (p.chunk * nw);
         const int lds = (4096 + 8192 + PTT_SAL_WAVES * 640) * (int)sizeof(float);
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_lds_kernel), lds))) return rc;
-        hipLaunchKernelGGL(sa_lds_kernel, dim3(wgs), dim3(64 * nw), lds, s, p);
+        if (d->compact_ws) {
+            // the balls' distinct rows first (sa_compact_kernel), then the MLP on 32-row tiles of 1 - 8 balls. The tile count
+            // is known on the device only: a fixed grid of at most one workgroup per CU walks it (as many tiles as balls at
+            // worst), so the call stays capturable with no host synchronisation
+            if (d->compact_ws_bytes < ptt_sa_compact_workspace(d->B, d->M) || (reinterpret_cast<uintptr_t>(d->compact_ws) & 15))
+                return fail(PTT_EWORKSPACE, "ptt_sa_fused_fwd_f32: compact_ws needs %zu bytes, 16-byte aligned (got %zu)",
+                            ptt_sa_compact_workspace(d->B, d->M), d->compact_ws_bytes);
+            p.cws = static_cast<int32_t*>(d->compact_ws);
+            hipLaunchKernelGGL(sa_compact_zero_kernel, dim3(1), dim3(64), 0, s, p.cws);
+            if ((rc = check_launch("sa_compact_zero_kernel"))) return rc;
+            hipLaunchKernelGGL(sa_compact_kernel, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
+                               SacTable{p.cws, total_centres});
+            if ((rc = check_launch("sa_compact_kernel"))) return rc;
+            if (wgs > 256 * PTT_SAL_WGS) wgs = 256 * PTT_SAL_WGS;
+            if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_lds_kernel<true>), lds))) return rc;
+            hipLaunchKernelGGL(sa_lds_kernel<true>, dim3(wgs), dim3(64 * nw), lds, s, p);
+            return check_launch("sa_lds_kernel");
+        }
+        if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_lds_kernel<false>), lds))) return rc;
+        hipLaunchKernelGGL(sa_lds_kernel<false>, dim3(wgs), dim3(64 * nw), lds, s, p);
         return check_launch("sa_lds_kernel");
     }
     // small weight set (fits L1/L2 comfortably) and <= 4 column tiles everywhere: barrier-free wave-private kernel

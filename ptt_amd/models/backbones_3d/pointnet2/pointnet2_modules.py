@@ -215,8 +215,11 @@ class PointnetSAModuleVotes(nn.Module):
                 new_features = ops.sa_fused_forward(xyz, new_xyz, idx, None, [L[:6] for L in layers[1:]], self.radius, True,
                                                     self.normalize_xyz, point_major_out=True, l0=(term, wx, relu0))
             else:
+                # the level without point features (SA0) pools each ball's distinct rows only: same bits, a fraction of
+                # the rows (ball-query padding and the resampled clouds' repeated points)
                 new_features = ops.sa_fused_forward(xyz, new_xyz, idx, features, [L[:6] for L in layers], self.radius,
-                                                    self.use_xyz, self.normalize_xyz, point_major_out=True)
+                                                    self.use_xyz, self.normalize_xyz, point_major_out=True,
+                                                    compact=features is None)
             return new_xyz, new_features, inds64
 
         hoist = (self.use_xyz and not self.sample_uniformly and self.nsample * npoint <= 16384

@@ -381,7 +381,7 @@ def linear(x, wpacked, cout, scale=None, shift=None, relu=False, residual=None, 
 
 
 def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, normalize_xyz=False,
-                     point_major_out=True, l0=None):
+                     point_major_out=True, l0=None, compact=False):
     """Fused group -> normalise -> SharedMLP(eval) -> max-pool (QueryAndGroup + SharedMLP + max_pool2d,
     pointnet2_utils.py:320-380, pytorch_utils.py:12-36, pointnet2_modules.py:84-88).
 
@@ -390,6 +390,9 @@ def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, 
     layers: list of (wpacked, scale|None, shift|None, cin, cout, relu); layers[0] packed with rot=3 if use_xyz.
     l0: optional (point_term (B,N,C0) contiguous, xyz_weight (3,C0), relu) — layer 0 hoisted to one row per point
     (include/ptt_hip.h, ptt_sa_desc.l0_*); then features must be None and `layers` are the remaining layers.
+    compact: the level without point features (SA0 shape) runs its MLP on every ball's distinct rows only, bitwise the
+    same output (ptt_sa_desc.compact_ws): True allocates the workspace, a device tensor of at least
+    ptt_sa_compact_workspace(B, M) bytes is used as it (afterwards it holds the ball table). Other shapes ignore it.
     Returns (B,Cout,M); with point_major_out it is a transposed view of (B,M,Cout) storage."""
     _chk(xyz, "xyz", torch.float32, 3)
     _chk(new_xyz, "new_xyz", torch.float32, 3)
@@ -433,6 +436,13 @@ def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, 
             raise RuntimeError("l0 point term must be (B,N,C0) and the xyz weight (3,C0)")
         d.l0_point_term, d.l0_xyz_weight = term.data_ptr(), wx.data_ptr()
         d.l0_channels, d.l0_relu = term.shape[2], int(bool(l0_relu))
+    if isinstance(compact, torch.Tensor):
+        if not compact.is_cuda or compact.device != xyz.device or not compact.is_contiguous():
+            raise RuntimeError("compact workspace must be a contiguous tensor on %s" % xyz.device)
+        d.compact_ws, d.compact_ws_bytes = compact.data_ptr(), compact.numel() * compact.element_size()
+    elif compact:
+        ws = _ws(_lib.lib().ptt_sa_compact_workspace(B, M), xyz.device)
+        d.compact_ws, d.compact_ws_bytes = ws.data_ptr(), ws.numel() * 8
     with torch.cuda.device(xyz.device), _timed('ptt_sa_fused_fwd_f32'):
         _lib.check(_lib.lib().ptt_sa_fused_fwd_f32(ctypes.byref(d), _stream()), "ptt_sa_fused_fwd_f32")
     return out
