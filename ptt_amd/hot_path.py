@@ -14,7 +14,7 @@ view of point-major rows).
 import torch
 import torch.nn as nn
 
-from . import graph_policy
+from . import graph_policy, ops
 from .graph_policy import graph_mode, set_graph_mode          # noqa: F401 — the switch lives here for callers (graph_policy.py)
 from .models.backbones_3d.pointnet2.pointnet2_modules import PointnetSAModuleVotes
 from .models.backbones_3d.pointnet2_backbone import PointNet2BackboneLight
@@ -125,34 +125,63 @@ class TrackerThroughput(object):
         return self.tracker(batch)
 
 
+def _watched(model, watch):
+    """The module whose state a graph of `model` reads: `watch` itself, nothing for watch=False, or by default `model` when it
+    is an nn.Module, the tracker of a TrackerThroughput."""
+    if watch is False:
+        return None
+    if watch is None:
+        watch = model.tracker if isinstance(model, TrackerThroughput) else model
+    return ops.StateWatch(watch) if isinstance(watch, nn.Module) else None
+
+
 class GraphedHotPath(object):
     """hipGraph replay of one hot-path step for fixed shapes (tracking and benchmarking run the same
     shapes every step): removes the per-kernel host launch cost and the gaps between ~60 dependent
-    launches. Inputs are copied into static buffers; outputs are the captured tensors."""
+    launches. Inputs are copied into static buffers; outputs are the captured tensors. A replay after the watched
+    module's weights or cached parameters changed (load_state_dict, training, train() / eval()) re-runs the warm-up and
+    captures again: the old graph addresses the old weights."""
 
-    def __init__(self, model, search_points, template_points, warmup=3):
+    def __init__(self, model, search_points, template_points, warmup=3, watch=None):
         """`model`: any callable (search (B,NS,3), template (B,NT,3)) -> outputs, e.g. FrameHotPath or a full tracker
-        wrapped as lambda s, t: tracker({'search_points': s, 'template_points': t})."""
+        wrapped as lambda s, t: tracker({'search_points': s, 'template_points': t}). `watch`: the nn.Module whose state the
+        graph reads (default: `model` if it is one, TrackerThroughput's tracker), False = the caller checks it."""
         self.model = model
         self.search = search_points.clone()
         self.template = template_points.clone()
+        self.warmup = warmup
+        self.watch = _watched(model, watch)
+        self.graph = self.out = None
+        self.captures = 0
+        self._capture()
+
+    def _capture(self):
+        model = self.model
+        if self.graph is not None:
+            torch.cuda.synchronize(self.search.device)   # the old graph's last replay is done before its pool is released
+        self.graph = self.out = None
         with torch.no_grad():
-            s = torch.cuda.Stream(device=search_points.device)
+            s = torch.cuda.Stream(device=self.search.device)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                for _ in range(warmup):                  # weight packing / LDS attributes happen here, not in capture
+                for _ in range(self.warmup):             # weight packing / LDS attributes happen here, not in capture
                     model(self.search, self.template)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with graph_policy.capture_scope(), torch.cuda.graph(self.graph):
                 self.out = model(self.search, self.template)
+        if self.watch is not None:
+            self.watch.mark()
+        self.captures += 1
 
     def __call__(self, search_points=None, template_points=None):
         if search_points is not None:
             self.search.copy_(search_points, non_blocking=True)
         if template_points is not None:
             self.template.copy_(template_points, non_blocking=True)
+        if self.watch is not None and self.watch.changed():
+            self._capture()
         self.graph.replay()
         return self.out
 
@@ -168,7 +197,9 @@ class PipelinedHotPath(object):
         out1 = pipe(search2, template2) ...
     """
 
-    def __init__(self, model, search_points, template_points, warmup=3):
+    def __init__(self, model, search_points, template_points, warmup=3, watch=None):
+        """`watch`: as GraphedHotPath's. A call after the watched state changed raises RuntimeError: the batch in flight was
+        sampled by the old graph, so a silent recapture could not tell which weights its result had."""
         self.model = model
         dev = search_points.device
         self.cur = [search_points.clone(), template_points.clone()]       # batch n (dense stage input)
@@ -197,8 +228,12 @@ class PipelinedHotPath(object):
                     dst.copy_(src)
                 for dst, src in zip(self.cur, self.nxt):
                     dst.copy_(src)
+        self.watch = _watched(model, watch)
 
     def __call__(self, next_search=None, next_template=None):
+        if self.watch is not None and self.watch.changed():
+            raise RuntimeError("PipelinedHotPath: the model's weights or cached parameters changed since the capture; "
+                               "build a new pipeline for them")
         if next_search is not None:
             self.nxt[0].copy_(next_search, non_blocking=True)
         if next_template is not None:
@@ -222,7 +257,7 @@ class InterleavedHotPath(object):
 
     The outputs belong to the stream in `pipe.last_stream`; make the consuming stream wait on it (or synchronise)."""
 
-    def __init__(self, model, search_points, template_points, ways=2, warmup=3):
+    def __init__(self, model, search_points, template_points, ways=2, warmup=3, watch=None):
         dev = search_points.device
         self.ways = int(ways)
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(self.ways)]
@@ -230,7 +265,7 @@ class InterleavedHotPath(object):
         for st in self.streams:
             st.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(st):
-                self.pipes.append(PipelinedHotPath(model, search_points, template_points, warmup=warmup))
+                self.pipes.append(PipelinedHotPath(model, search_points, template_points, warmup=warmup, watch=watch))
         torch.cuda.synchronize(dev)
         self.calls = 0
         self.last_stream = self.streams[0]

@@ -94,6 +94,8 @@ class PointnetSAModuleVotes(nn.Module):
     def train(self, mode=True):
         # a train-mode forward updates the BatchNorm running statistics through raw pointers on some torch builds
         # (no _version bump): drop the folded / packed parameters whenever the mode changes
+        if getattr(self, '_fused_cache', None) is not None:
+            ops.drop_params()
         self._fused_cache = None
         return super().train(mode)
 
@@ -174,7 +176,7 @@ class PointnetSAModuleVotes(nn.Module):
             if key not in self._arange_cache:          # search and template branches alternate (B, npoint)
                 self._arange_cache[key] = torch.arange(npoint, dtype=torch.int64, device=xyz.device).repeat(
                     xyz.size(0), 1)
-                ops.publish_params(xyz.device)
+                ops.publish_params(xyz.device, replaced=False)
             inds64 = self._arange_cache[key]
         elif inds is None:
             inds = self._sample(xyz, features, npoint)

@@ -73,7 +73,7 @@ class PointNet2BackboneLight(nn.Module):
         cache = self.__dict__.setdefault('_arange_cache', {})
         if key not in cache:
             cache[key] = torch.arange(n, dtype=torch.int64, device=xyz.device).repeat(xyz.size(0), 1)
-            ops.publish_params(xyz.device)
+            ops.publish_params(xyz.device, replaced=False)
         return cache[key]
 
     def branch_forward(self, pts, npoints: List, inds0=None, want_knn=0):

@@ -58,6 +58,8 @@ class CosineSimAug(nn.Module):
         return True
 
     def train(self, mode=True):
+        if getattr(self, '_cache', None) is not None:
+            ops.drop_params()
         self._cache = None          # BatchNorm running statistics may change without a _version bump in train mode
         return super().train(mode)
 

@@ -87,13 +87,48 @@ def note_unfused(name, reason):
     return False
 
 
-def publish_params(device):
+param_generation = 0        # bumped whenever a module replaces or drops a cached set of packed / folded parameters
+
+
+def publish_params(device, replaced=True):
     """Called by the modules right after they (re)build a cached set of packed / folded parameters: blocks the host
     until the kernels that produced them have finished. The caches are shared by every stream that later runs the
     module (the search and template branches run on two streams and share their SA modules), and a cache entry built
-    on one stream must not be read by a kernel on another stream before it is complete. Once per weight version."""
+    on one stream must not be read by a kernel on another stream before it is complete. Once per weight version.
+    replaced: the new entry takes the place of an older one, whose buffers a captured graph may still address
+    (param_generation moves); False for caches that only ever grow (per-shape index tables)."""
+    global param_generation
+    if replaced:
+        param_generation += 1
     if device.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
         torch.cuda.current_stream(device).synchronize()
+
+
+def drop_params():
+    """Called by a module that drops its cached parameters (train(): the running statistics are about to move): the
+    buffers a captured graph read are being freed."""
+    global param_generation
+    param_generation += 1
+
+
+class StateWatch(object):
+    """What a captured graph read of a module's state, as of the capture: (data_ptr, _version) of every parameter and
+    buffer, and param_generation. changed() -> True once the weights were written (load_state_dict, an optimiser step,
+    a replayed training step) or a cache of packed / folded parameters was rebuilt or dropped since: replaying the graph
+    would then compute with the old weights, or read freed memory."""
+
+    def __init__(self, module):
+        self.tensors = list(module.parameters()) + list(module.buffers())
+        self.mark()
+
+    def _key(self):
+        return list(map(torch.Tensor.data_ptr, self.tensors)), [t._version for t in self.tensors]
+
+    def mark(self):
+        self.generation, self.key = param_generation, self._key()
+
+    def changed(self):
+        return param_generation != self.generation or self._key() != self.key
 
 
 def require_finite(*tensors):
@@ -664,7 +699,7 @@ def mt19937_draws(device, n=8192, seed=1):
         host = np.empty(int(n), np.uint32)
         _lib.check(_lib.lib().ptt_mt19937_fill(int(seed), host.ctypes.data, int(n)), "ptt_mt19937_fill")
         _mt_tables[key] = torch.from_numpy(host.view(np.int32)).to(device)
-        publish_params(torch.device(device))
+        publish_params(torch.device(device), replaced=False)
     return _mt_tables[key]
 
 

@@ -85,6 +85,7 @@ class TrackletRunner(object):
         self._model = _BoxedForward(tracker, select=not self.few)
         self._graph = None
         self._frame = None                                           # few tracklets: crops + resampling + model + read-backs, one graph
+        self._watch = None                                           # the tracker's state as of the graph's capture (ops.StateWatch)
         self._done = torch.cuda.Event()
         self.stream = None                                           # run_overlapped gives every runner its own stream
         self.profile = None       # set to {} before run(): per-frame host_pre / device / host_post milliseconds are appended
@@ -328,6 +329,7 @@ class TrackletRunner(object):
                 with graph_policy.capture_scope(), torch.cuda.graph(self._frame):
                     self._frame_body()
                     self.readback_host.copy_(self.readback, non_blocking=True)
+                self._watch = ops.StateWatch(self.tracker)
             finally:
                 head.pred_box_out = None                     # the tracker may be shared: the hook is only live during capture
 
@@ -338,8 +340,16 @@ class TrackletRunner(object):
             return                                           # the frame graph (_capture_frame) holds the model
         if self.use_graph and self._graph is None:
             with torch.no_grad():
-                self._graph = GraphedHotPath(self._model, self.search, self.template)
+                self._graph = GraphedHotPath(self._model, self.search, self.template, watch=False)     # run() checks the tracker
             self.search, self.template = self._graph.search, self._graph.template
+            self._watch = ops.StateWatch(self.tracker)
+
+    def _drop_stale_graphs(self):
+        """Once per run (the weights cannot change inside one): a graph captured before the tracker's weights or cached parameters
+        changed (load_state_dict, training, train() / eval()) would replay the old weights, or read freed buffers — it is dropped
+        and captured again at the next frame."""
+        if self._watch is not None and self._watch.changed():
+            self._frame = self._graph = self._watch = None
 
     def _forward(self):
         with torch.no_grad():
@@ -352,6 +362,7 @@ class TrackletRunner(object):
         """tracklets: list of (clouds, boxes) as in `_load`. Returns, per tracklet, the list of result boxes
         [(center, wlh, quat[, score]), ...] — element 0 is the frame-0 ground-truth box, as in the reference
         (eval_tracking_utils.py:96-100)."""
+        self._drop_stale_graphs()
         out = []
         for g in range(0, len(tracklets), self.B):
             out.extend(self._run_group(tracklets[g:g + self.B]))
@@ -373,6 +384,7 @@ def run_overlapped(runners, tracklets):
     for r in runners:
         if r.stream is None:
             r.stream = torch.cuda.Stream(device=dev)
+        r._drop_stale_graphs()
     # deal whole groups round-robin: runner k takes groups k, k+R, ...
     order, per_runner = [], [[] for _ in runners]
     pos = 0

@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 
 from . import synth
-from .optim import ClipAdam
+from .optim import ClipAdam, _bump_versions
 
 GRAD_ELEMS = 4903113            # parameters of the shipped PTT model
 
@@ -80,7 +80,7 @@ class _CapturedStep(object):
         self.signature = self._signature(batch)
         self.first, self.second = torch.cuda.CUDAGraph(), None
         self.loss, self.tables, self.optimizer_state, self.packs = None, None, None, None
-        self.loaded = {}                  # key -> (data_ptr, version) of the caller's tensor the static copy holds
+        self.bn_buffers = []              # running statistics the recorded launches update through raw pointers
 
     @staticmethod
     def _signature(batch):
@@ -93,14 +93,12 @@ class _CapturedStep(object):
         return trainer.optimizer._graph is not None and trainer.optimizer._graph is self.optimizer_state
 
     def load(self, batch):
-        """The batch into the static tensors the graphs read; a tensor that is the very one loaded last time, unmodified since
-        (same storage, same version counter), is not copied again."""
-        for k, v in batch.items():
-            if torch.is_tensor(v):
-                tag = (v.data_ptr(), v._version)
-                if self.loaded.get(k) != tag:
-                    self.static[k].copy_(v, non_blocking=True)
-                    self.loaded[k] = tag
+        """The batch into the static tensors the graphs read, always copied (one call, four device-to-device copies under 1 MB).
+        Neither (data_ptr, _version) nor the tensor's identity tells a new batch from the last one: a batch moved to the device
+        after the previous one was freed gets its block back with a fresh version counter, and a raw-pointer writer refills a
+        buffer without moving it."""
+        keys = [k for k, v in batch.items() if torch.is_tensor(v)]
+        torch._foreach_copy_([self.static[k] for k in keys], [batch[k] for k in keys], non_blocking=True)
 
 
 class DataParallelTrainer(object):
@@ -255,6 +253,9 @@ class DataParallelTrainer(object):
             warnings.warn("DataParallelTrainer: capturing the training step failed (%s: %s); stepping eagerly" % (type(e).__name__, e))
             return
         cap.optimizer_state = self.optimizer._graph
+        cap.bn_buffers = [t for m in self.tracker.modules()
+                          if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training and m.track_running_stats
+                          for t in (m.running_mean, m.running_var, m.num_batches_tracked) if t is not None]
         self.captured = cap
 
     def _replay(self, batch):
@@ -267,6 +268,8 @@ class DataParallelTrainer(object):
                 self._reduce()
             cap.second.replay()
         self.optimizer.end_graph_step()
+        # the replay moved the running statistics through raw pointers; the eval-mode parameter caches key on their versions
+        _bump_versions(cap.bn_buffers)
         self.tracker.update_global_step()
         self.graph_steps += 1
         return cap.loss
