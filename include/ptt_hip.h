@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 22
+#define PTT_ABI_VERSION 23
 
 enum {
     PTT_OK = 0,
@@ -424,6 +424,10 @@ int ptt_spatial_order_f32(const float* xyz, int B, int N, int32_t* order, ptt_st
  *   the ground-truth box — get_label_by_box (:238-272) evaluated on the first crop's points in the CLOUD's frame, i.e.
  *   p' = float32(lrot . float32(p + ltrans)), llo < p' < lhi with the ground-truth box's own translation / rotation / bounds —
  *   carried through the second crop exactly as crop_pc carries `label` (:295-296).
+ *   append != 0 (SHAPE_AGGREGATION = all, whose template is get_model over every earlier frame, eval_tracking_utils.py:211-216):
+ *   `out` already holds the crops of earlier launches and *count their running total; this crop's survivors are written after
+ *   them (rows from `capacity` on are counted, not written) and *count is raised by their number. The total stays on the
+ *   device, so a replayed job table needs no host-side offset; running the same job twice appends twice.
  * ------------------------------------------------------------------------------- */
 typedef struct ptt_crop_job {
     const float* points;        /* (3, n_points) float32: row 0 = x, row 1 = y, row 2 = z (PointCloud.points) */
@@ -440,6 +444,8 @@ typedef struct ptt_crop_job {
     double ltrans[3];           /* ... whose frame is p' = lrot . (p + ltrans), bounds llo < p' < lhi */
     double lrot[9];
     double llo[3], lhi[3];
+    int32_t append;             /* 0: survivors from row 0, *count = their number; nonzero: appended to a running store (above) */
+    int32_t reserved;           /* 0 */
 } ptt_crop_job;
 
 int ptt_crop_compact_f32(const ptt_crop_job* jobs_device, int n_jobs, ptt_stream_t stream);

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libptt_hip.so")
 
 PTT_SA_MAX_LAYERS = 4
-ABI_VERSION = 22            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
+ABI_VERSION = 23            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
 
 # every symbol include/ptt_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -55,7 +55,8 @@ class CropJob(Structure):
                 ("lo1", c_double * 3), ("hi1", c_double * 3), ("trans", c_double * 3), ("rot", c_double * 9),
                 ("lo2", c_double * 3), ("hi2", c_double * 3),
                 ("out", c_void_p), ("count", c_void_p), ("n_points", c_int32), ("capacity", c_int32),
-                ("label_out", c_void_p), ("ltrans", c_double * 3), ("lrot", c_double * 9), ("llo", c_double * 3), ("lhi", c_double * 3)]
+                ("label_out", c_void_p), ("ltrans", c_double * 3), ("lrot", c_double * 9), ("llo", c_double * 3), ("lhi", c_double * 3),
+                ("append", c_int32), ("reserved", c_int32)]
 
 
 class RegularizeJob(Structure):

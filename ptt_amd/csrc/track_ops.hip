@@ -62,14 +62,22 @@ __device__ __forceinline__ int block_rank(bool flag, int* wsum, int& total) {
     return base + below;
 }
 
-// One workgroup per crop job: a stable stream compaction over the cloud in chunks of T points.
+// One workgroup per crop job: a stable stream compaction over the cloud in chunks of T points. An append job (a running
+// store of earlier crops, SHAPE_AGGREGATION = all) starts at the store's total instead of row 0.
 template <int T>
 __device__ __forceinline__ void crop_compact_body(const ptt_crop_job& j) {
     __shared__ int wsum[T / 64];
+    __shared__ int start;
     const float* px = j.points;
     const float* py = j.points + j.ld;
     const float* pz = j.points + 2 * j.ld;
     int written = 0;
+    if (j.append) {                                  // uniform over the workgroup
+        // lane 0 alone reads the running total and (below) writes the new one: no other lane touches *count
+        if (threadIdx.x == 0) start = *j.count;
+        __syncthreads();
+        written = start;
+    }
     for (int base = 0; base < j.n_points; base += T) {
         const int i = base + (int)threadIdx.x;
         bool keep = false, label = false;
@@ -113,7 +121,7 @@ __device__ __forceinline__ void crop_compact_body(const ptt_crop_job& j) {
         }
         written += total;
     }
-    if (threadIdx.x == 0) *j.count = written;       // may exceed capacity: the caller sized `out` for n_points
+    if (threadIdx.x == 0) *j.count = written;       // may exceed capacity: the caller sized `out` for n_points (+ the store)
 }
 
 template <int T>

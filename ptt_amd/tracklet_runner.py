@@ -20,14 +20,45 @@ every tracklet per step:
 At batch = 1 this is the reference's own mode (one tracklet, one frame at a time) with the per-frame PCIe traffic cut
 to ~0.5 KB; at batch = 48 it is the throughput mode for evaluating a dataset's tracklets.
 
-REF_BOX = previous_result and SHAPE_AGGREGATION = firstandprevious (the shipped tools/cfgs/*/ptt.yaml:149-150) are what
-is implemented.
+The evaluator's two TEST settings (tools/cfgs/*/ptt.yaml:149-150) are arguments, parsed as the reference parses them
+(tracking_modes):
+    REF_BOX            previous_result (shipped) / previous_gt / current_gt: the box the search area is cropped around and
+                       the box update starts from (prepare_search :155-162, post_process :270); a result taken from a
+                       ground-truth box keeps that box's wlh.
+    SHAPE_AGGREGATION  firstandprevious (shipped) / first / previous / all: which earlier frames' crops (always around the
+                       RESULT boxes) make the template (prepare_template :186-216). first / previous resample one crop slot;
+                       all keeps a per-tracklet store of the crops of frames 0..i-1 in HBM to which the template crop job
+                       APPENDS cloud i-1 (ptt_crop_job.append): one crop per frame, the launches of firstandprevious.
+The defaults are the shipped pair, with the launches and results they had before the settings existed.
 """
 import numpy as np
 import torch
 
 from . import graph_policy, ops
 from .hot_path import GraphedHotPath, TrackerThroughput
+
+
+SHAPE_AGGREGATIONS = ("firstandprevious", "first", "previous", "all")
+REF_BOXES = ("previous_result", "previous_gt", "current_gt")
+
+
+def tracking_modes(shape_aggregation="firstandprevious", ref_box="previous_result"):
+    """cfg.TEST.SHAPE_AGGREGATION, cfg.TEST.REF_BOX -> (one of SHAPE_AGGREGATIONS, one of REF_BOXES), read as the reference reads
+    them: a case-insensitive substring test in the reference's order (prepare_template, eval_tracking_utils.py:187-216: anything
+    without FIRST / PREVIOUS is `all`, and "first_and_previous" is `first`; prepare_search :156-162: anything else raises)."""
+    agg, ref = str(shape_aggregation).upper(), str(ref_box).upper()
+    if "FIRSTANDPREVIOUS" in agg:
+        shape = "firstandprevious"
+    elif "FIRST" in agg:
+        shape = "first"
+    elif "PREVIOUS" in agg:
+        shape = "previous"
+    else:
+        shape = "all"
+    for name in REF_BOXES:
+        if name.upper() in ref:
+            return shape, name
+    raise ValueError("reference_BB must be set with previous_result/previous_gt/current_gt")
 
 
 class _BoxedForward(object):
@@ -47,10 +78,13 @@ class _BoxedForward(object):
 
 class TrackletRunner(object):
     def __init__(self, tracker, device, batch=1, search_size=1024, template_size=512, search_offset=0.0,
-                 search_scale=1.25, model_offset=0.0, model_scale=1.25, use_z=True, use_graph=True):
+                 search_scale=1.25, model_offset=0.0, model_scale=1.25, use_z=True, use_graph=True,
+                 shape_aggregation="firstandprevious", ref_box="previous_result"):
         """`tracker`: ptt_amd.models.trackers.PTT in eval mode on `device`. Sizes / offsets / scales are
         DATA_CONFIG.{SEARCH,TEMPLATE}_INPUT_SIZE, SEARCH_BB_*, MODEL_BB_* and USE_Z_AXIS
-        (tools/cfgs/kitti_models/ptt.yaml:8-17)."""
+        (tools/cfgs/kitti_models/ptt.yaml:8-17); shape_aggregation / ref_box are TEST.SHAPE_AGGREGATION / TEST.REF_BOX
+        (:149-150), parsed by tracking_modes."""
+        self.shape, self.ref_box = tracking_modes(shape_aggregation, ref_box)
         self.tracker = tracker
         self.device = torch.device(device)
         self.B = int(batch)
@@ -87,6 +121,10 @@ class TrackletRunner(object):
         self._frame = None                                           # few tracklets: crops + resampling + model + read-backs, one graph
         self._watch = None                                           # the tracker's state as of the graph's capture (ops.StateWatch)
         self._done = torch.cuda.Event()
+        # SHAPE_AGGREGATION = all: per tracklet the canonical-frame crops of frames 0..i-1, (B, capacity, 3), and their running
+        # totals (device scalars the append crop raises; the host learns them from the template's read-back info[0])
+        self.store = self.store_count = None
+        self.store_growths = 0                                       # how often a store was enlarged (over the runner's life)
         self.stream = None                                           # run_overlapped gives every runner its own stream
         self.profile = None       # set to {} before run(): per-frame host_pre / device / host_post milliseconds are appended
 
@@ -131,6 +169,12 @@ class TrackletRunner(object):
         for dst, src in zip(ff, (self.ptr, self.ld, self.npts)):
             dst[:, 0::2] = src
             dst[1:, 1::2] = src[:-1]
+        if self.shape == "first":
+            ff[2][:, 1::2] = 0                                     # the template is frame 0's crop alone: no per-frame crop
+        elif self.shape == "all":
+            # a finished tracklet appends nothing (its frame `length` would otherwise add cloud length - 1 to its store)
+            lengths = np.array([len(c) for c, _ in tracklets] + [0] * (B - len(tracklets)))
+            ff[2][:, 1::2] *= (np.arange(T)[:, None] < lengths[None, :])
         self.frame_fields = ff
         # the resampling jobs never change within a group: fixed segment / output pointers
         rj = np.zeros(2 * B, ops.REGULARIZE_JOB)
@@ -139,12 +183,55 @@ class TrackletRunner(object):
         s['n_seg'], s['input_size'] = 1, self.S
         s['out'] = self.search.data_ptr() + np.arange(B) * (self.S * 3 * 4)
         s['info'] = self.info.data_ptr() + np.arange(B) * 16
-        for k, slot in enumerate((1, 2)):                          # get_model([PC_0, PC_{i-1}], ...) order (:189-194)
+        # the template's segments in get_model's order (prepare_template :187-216): firstandprevious [PC_0, PC_{i-1}], first [PC_0],
+        # previous [PC_{i-1}] — slot 1 holds frame 0's crop, slot 2 the per-frame crop; all: the tracklet's store (_store_tables)
+        slots = {"firstandprevious": (1, 2), "first": (1,), "previous": (2,), "all": ()}[self.shape]
+        for k, slot in enumerate(slots):
             t['seg'][:, k], t['seg_count'][:, k], t['seg_capacity'][:, k] = self.out_ptr[:, slot], self.cnt_ptr[:, slot], cap
-        t['n_seg'], t['input_size'] = 2, self.T
+        t['n_seg'], t['input_size'] = max(1, len(slots)), self.T
         t['out'] = self.template.data_ptr() + np.arange(B) * (self.T * 3 * 4)
         t['info'] = self.info.data_ptr() + np.arange(B) * 16 + 8
-        ops.upload_jobs(rj, self.reg_jobs_dev)
+        self.reg_jobs = rj
+        if self.shape == "all":
+            # every group starts with an empty store; a store that grew in an earlier group keeps its capacity
+            if self.store is None or self.store.shape[1] < cap:
+                self.store = torch.zeros((B, cap, 3), dtype=torch.float32, device=dev)
+                self.store_count = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.store_count.zero_()
+            self.store_total = np.zeros(B, np.int64)
+            self._store_tables()                                   # uploads the resampling table
+        else:
+            ops.upload_jobs(rj, self.reg_jobs_dev)
+
+    def _store_tables(self):
+        """SHAPE_AGGREGATION = all: point the template crop jobs (odd entries of the pinned crop table: append into the store) and
+        the template resampling jobs (one segment: the whole store, its count the running total) at the current store, and upload
+        the resampling table. A captured frame graph reads both tables when it replays (the crop table from pinned memory, the
+        resampling table from device memory), so a store that moved needs this upload, not a new capture."""
+        B, cap = self.B, self.store.shape[1]
+        ptr = (self.store.data_ptr() + np.arange(B) * (cap * 3 * 4)).astype(np.uint64)
+        cnt = (self.store_count.data_ptr() + np.arange(B) * 4).astype(np.uint64)
+        t = self.reg_jobs[1::2]
+        t['seg'][:, 0], t['seg_count'][:, 0], t['seg_capacity'][:, 0] = ptr, cnt, cap
+        self.store_jobs = (ptr, cnt, cap)
+        ops.upload_jobs(self.reg_jobs, self.reg_jobs_dev)
+
+    def _reserve_store(self, i):
+        """Before frame i appends cloud i - 1: every store must hold its total plus all of that cloud's points (a crop keeps
+        at most those), so that no point is ever dropped. Otherwise the stores grow geometrically: a new buffer, a device copy
+        of the used rows, new job pointers (_store_tables); the host waited for frame i - 1, so nothing reads the old buffer."""
+        need = int((self.store_total + self.frame_fields[2][i, 1::2]).max())
+        cap = self.store.shape[1]
+        if need <= cap:
+            return
+        used = int(self.store_total.max())
+        grown = torch.empty((self.B, max(need, 2 * cap), 3), dtype=torch.float32, device=self.device)
+        grown[:, :used].copy_(self.store[:, :used])
+        self.store = grown
+        self.store_growths += 1
+        self._store_tables()
+        jobs = self.crop_jobs_host_np[1::2]
+        jobs['out'], jobs['capacity'] = self.store_jobs[0], self.store_jobs[2]
 
     def _crop_jobs(self, frame_a, slot_a, cfg_a, frame_b, slot_b, cfg_b, launch=True):
         """The 2B-entry crop table of one step, built in the pinned staging buffer and copied to the device: job 2b =
@@ -154,7 +241,7 @@ class TrackletRunner(object):
         jobs = self.crop_jobs_host_np
         for k, (frame, slot, cfg) in enumerate(((frame_a, slot_a, cfg_a), (frame_b, slot_b, cfg_b))):
             half = jobs[k::2]
-            half['out'], half['count'] = self.out_ptr[:, slot], self.cnt_ptr[:, slot]
+            half['out'], half['count'], half['append'] = self.out_ptr[:, slot], self.cnt_ptr[:, slot], 0
             if frame is None or frame >= self.ptr.shape[0]:
                 half['points'], half['n_points'] = self.crop_out.data_ptr(), 0
                 continue
@@ -168,15 +255,17 @@ class TrackletRunner(object):
             self.crop_jobs_dev.copy_(self.crop_jobs_host, non_blocking=True)
             ops.crop_compact(self.crop_jobs_dev, 2 * self.B)
 
-    def _frame_jobs(self, i, extra2):
+    def _frame_jobs(self, i, extra2, ref=None):
         """The crop table of tracked frame i >= 1 written into the pinned staging buffer with three array assignments and two
-        calls: job 2b = cloud i of tracklet b around its current box into slot 0 (the search crop, `extra2` = gt_wlh1 * 0.6),
-        job 2b + 1 = cloud i - 1 into slot 2 (get_model's previous-frame segment). The per-frame cloud fields were laid out for
+        calls: job 2b = cloud i of tracklet b around its reference box into slot 0 (the search crop, `extra2` = gt_wlh1 * 0.6;
+        `ref` = the REF_BOX boxes, None = the current results), job 2b + 1 = cloud i - 1 around its current result into slot 2
+        (get_model's previous-frame segment) or appended to its store (all). The per-frame cloud fields were laid out for
         all frames by _load (self.frame_fields); `out` / `count` were set for these slots once (_steps)."""
         jobs = self.crop_jobs_host_np
         pts, ld, npts = self.frame_fields
         jobs['points'], jobs['ld'], jobs['n_points'] = pts[i], ld[i], npts[i]
-        ops.track_crop_bounds(self.boxes, self.search_offset, self.search_scale, extra2, jobs[0::2], job_stride=2)
+        ops.track_crop_bounds(self.boxes if ref is None else ref, self.search_offset, self.search_scale, extra2, jobs[0::2],
+                              job_stride=2)
         ops.track_crop_bounds(self.boxes, self.model_offset, self.model_scale, None, jobs[1::2], job_stride=2)
 
     def _launch_jobs(self):
@@ -200,18 +289,27 @@ class TrackletRunner(object):
         boxes = self.boxes = np.zeros(B, ops.TRACK_BOX)
         boxes['wlh'], boxes['quat'][:, 0] = 1.0, 1.0
         gt_wlh1 = np.zeros((T, B))
+        gt = None
+        if self.ref_box != "previous_result":
+            gt = np.zeros((T, B), ops.TRACK_BOX)                 # REF_BOX previous_gt / current_gt: frame i's reference box
+            gt['wlh'], gt['quat'][..., 0] = 1.0, 1.0              # (frames past a tracklet's end: a unit box, never used)
         for b, (_, gts) in enumerate(tracklets):
             boxes['center'][b], boxes['wlh'][b], boxes['quat'][b] = gts[0][0], gts[0][1], gts[0][2]
             for i, bx in enumerate(gts):
                 gt_wlh1[i, b] = bx[1][1]
+                if gt is not None:
+                    gt['center'][i, b], gt['wlh'][i, b], gt['quat'][i, b] = bx[0], bx[1], bx[2]
         self.crop_jobs_host_np['capacity'] = self.cap
-        wlh0 = boxes['wlh'].copy()
-        history = [(np.ones(B, np.int32), boxes['center'].copy(), boxes['quat'].copy(), None)]   # per step: whole-batch copies
+        # per step: whole-batch copies (a result taken from a ground-truth reference box carries that box's wlh)
+        history = [(np.ones(B, np.int32), boxes['center'].copy(), boxes['wlh'].copy(), boxes['quat'].copy(), None)]
         rng_pos = np.zeros(B, np.int64)            # where numpy's global generator stands for each tracklet
         model_cfg = (self.model_offset, self.model_scale, None)
 
-        # frame 0: the first-frame template crop (get_model's first segment) is fixed for the whole tracklet
-        self._crop_jobs(0, 1, model_cfg, None, 2, model_cfg)
+        # frame 0: the first-frame template crop (get_model's first segment, slot 1) is fixed for the whole tracklet. Only
+        # firstandprevious and first read slot 1: previous resamples slot 2 alone, and all takes frame 0's crop from its store,
+        # to which frame 1 appends it — no launch for those two
+        if self.shape in ("firstandprevious", "first"):
+            self._crop_jobs(0, 1, model_cfg, None, 2, model_cfg)
         # the job table travels through ONE pinned staging buffer: its copy must have left the host before frame 1's
         # table is written into it (every later frame waits for its boxes anyway)
         self._done.record(torch.cuda.current_stream(self.device))
@@ -220,6 +318,10 @@ class TrackletRunner(object):
         jobs = self.crop_jobs_host_np
         jobs['out'][0::2], jobs['count'][0::2] = self.out_ptr[:, 0], self.cnt_ptr[:, 0]
         jobs['out'][1::2], jobs['count'][1::2] = self.out_ptr[:, 2], self.cnt_ptr[:, 2]
+        jobs['append'] = 0
+        if self.shape == "all":                                  # ... or the template crop appends to the tracklet's store
+            jobs['out'][1::2], jobs['count'][1::2], jobs['capacity'][1::2] = self.store_jobs
+            jobs['append'][1::2] = 1
         extra_search = np.ascontiguousarray(gt_wlh1 * 0.6)        # (T, B): gt_box.wlh[1] * 0.6 enters the search crop (:321)
         est_buf = np.zeros((B, 5), np.float32)
         active_all = (np.arange(T)[:, None] < lengths[None, :]).astype(np.int32)
@@ -236,17 +338,21 @@ class TrackletRunner(object):
                 t_a = time.perf_counter()
                 ev0.record(torch.cuda.current_stream(self.device))
             active = active_all[i]
-            # both crops of frame i are taken around the previous RESULT box (prepare_search :156-157, prepare_template
-            # :189-194 with results_BBs[frame_id - 1]); a finished tracklet's later frames have n_points 0
+            # the search crop of frame i is taken around the REF_BOX (prepare_search :156-162: by default the previous result),
+            # the template crop around the previous RESULT (prepare_template :187-216 with results_BBs[frame_id - 1]); a finished
+            # tracklet's later frames have n_points 0
+            ref = None if gt is None else gt[i - 1] if self.ref_box == "previous_gt" else gt[i]
+            if self.shape == "all":
+                self._reserve_store(i)
             if self.few and self.use_graph:
                 # a handful of tracklets: the WHOLE frame is one hipGraph replay — crops (their table read from pinned host
                 # memory, rewritten here), resampling, read-back of the draw counts, tracker, read-back of the proposals
-                self._frame_jobs(i, extra_search[i])
+                self._frame_jobs(i, extra_search[i], ref)
                 if self._frame is None:
                     self._capture_frame()
                 self._frame.replay()
             else:
-                self._frame_jobs(i, extra_search[i])
+                self._frame_jobs(i, extra_search[i], ref)
                 self._launch_jobs()
                 ops.regularize(self.reg_jobs_dev, 2 * B, self.draws)
                 self.info_host.copy_(self.info, non_blocking=True)   # behind the resampling, ahead of the model: off the frame's tail
@@ -274,8 +380,13 @@ class TrackletRunner(object):
             # (B,P,5) (:267-269), box_i = get_box_by_offset(box_{i-1}, best proposal, USE_Z_AXIS). An implausibly large x / y offset
             # is redrawn from numpy's GLOBAL generator (:205-208), whose state then is "seeded with 1 and advanced by the template's
             # (else the search's) resampling draws" — the draw counts come back with the boxes; a draw table that ran out raises
+            if ref is not None:                                  # post_process :270 moves the REF box (and keeps its wlh)
+                live = active.astype(bool)
+                boxes[live] = ref[live]
             ops.track_select_update(est, info, boxes, self.use_z, active, rng_pos, est_buf)
-            history.append((active, boxes['center'].copy(), boxes['quat'].copy(), est_buf[:, 4].copy()))
+            if self.shape == "all":                              # the template's n is the store's new total (one segment)
+                self.store_total[:] = info[:, 1, 0]
+            history.append((active, boxes['center'].copy(), boxes['wlh'].copy(), boxes['quat'].copy(), est_buf[:, 4].copy()))
             if prof is not None:
                 t_d = time.perf_counter()
                 ev1.synchronize()
@@ -283,13 +394,13 @@ class TrackletRunner(object):
                 prof['device_ms'].append(ev0.elapsed_time(ev1))      # crop + resample + model graph + read-back, on the device
                 prof['host_post_ms'].append((t_d - t_c) * 1e3)       # float64 box update, history
                 prof['frame_ms'].append((t_d - t_a) * 1e3)
-        # per-tracklet result lists, assembled once (three array copies per step instead of 3 x B small ones)
+        # per-tracklet result lists, assembled once (four array copies per step instead of 4 x B small ones)
         results = []
         for b in range(n):
             rows = []
-            for act, c, q, sc in history:
+            for act, c, wlh, q, sc in history:
                 if act[b]:
-                    rows.append((c[b], wlh0[b], q[b]) if sc is None else (c[b], wlh0[b], q[b], float(sc[b])))
+                    rows.append((c[b], wlh[b], q[b]) if sc is None else (c[b], wlh[b], q[b], float(sc[b])))
             results.append(rows)
         return results
 
@@ -317,6 +428,10 @@ class TrackletRunner(object):
         with torch.no_grad():
             cur = torch.cuda.current_stream(self.device)
             side = torch.cuda.Stream(device=self.device)
+            # SHAPE_AGGREGATION = all: each warm-up run appends frame i - 1's crop to the stores once more — their totals are
+            # put back afterwards, so that the replay below appends it once (what the extra runs wrote past them is overwritten).
+            # The copy is taken on `cur` BEFORE `side` waits for it: the warm-ups on `side` are then ordered after it
+            totals = self.store_count.clone() if self.shape == "all" else None
             side.wait_stream(cur)
             head.pred_box_out = self.readback[:self.n_box].view(self.B, self.P, 5)
             try:
@@ -325,6 +440,8 @@ class TrackletRunner(object):
                         rows = self._frame_body()
                 cur.wait_stream(side)
                 torch.cuda.synchronize(self.device)
+                if totals is not None:
+                    self.store_count.copy_(totals)
                 self._frame = torch.cuda.CUDAGraph()
                 with graph_policy.capture_scope(), torch.cuda.graph(self._frame):
                     self._frame_body()
