@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 23
+#define PTT_ABI_VERSION 24
 
 enum {
     PTT_OK = 0,
@@ -401,6 +401,10 @@ typedef struct ptt_attn_desc {
     int B, N, k, D;
     const int32_t* order;  /* (B,N) from ptt_spatial_order_f32, or NULL: which flat point (b*N + n) launch slot s works on. A
                               permutation inside every cloud; results do not depend on it (L2 locality of the k | v gathers) */
+    int heads;             /* 0 or 1: TransformerBlock. 2, 4, 8: MulHeadTransformerLayer (multitransformer.py:11-63) with
+                              hd = D / heads: Wg1p / Wg2p are the packed hd x hd fc_gamma weights that every head shares, bg1
+                              is fc_gamma[0].bias repeated `heads` times (D floats), the softmax scale is 1 / sqrt(hd), and
+                              attn is written in the reference's (B*heads, N, k, hd) layout                                  */
 } ptt_attn_desc;
 
 int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream);
@@ -651,6 +655,11 @@ int ptt_linear_batched_f32(const float* X, int rows, int K, int ldx, int64_t x_b
                            const float* residual, int ldr, int64_t r_batch_stride, float* out, int ldo,
                            int64_t o_batch_stride, int batch, ptt_stream_t stream);
 int ptt_softmax_rows_f32(float* X, int64_t rows, int n, int ld, float scale, ptt_stream_t stream);
+/* out = LayerNorm_C(x) (+ residual): nn.LayerNorm(C) over the rows of a (rows, C) matrix (multitransformer.py:59-60 norm1,
+ * norm2), one wave per row, fp32, mean then the variance of the centred values; weight / bias / residual may be NULL.
+ * C <= 1024. out may alias x. */
+int ptt_layernorm_f32(const float* x, int rows, int C, int ldx, const float* weight, const float* bias, float eps,
+                      const float* residual, int ldr, float* out, int ldo, ptt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * N3  the row GEMMs of the training step at 10^4 - 10^6 rows (round 3): a persistent, software-pipelined form of

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libptt_hip.so")
 
 PTT_SA_MAX_LAYERS = 4
-ABI_VERSION = 23            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
+ABI_VERSION = 24            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
 
 # every symbol include/ptt_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -25,7 +25,7 @@ EXPORTS = [
     "ptt_track_crop_bounds", "ptt_track_box_by_offset",
     "ptt_bn_stats_workspace", "ptt_bn_stats_f32", "ptt_bn_apply_f32", "ptt_bn_bwd_f32", "ptt_pool_rows_f32",
     "ptt_pool_rows_bwd_f32", "ptt_linear_wgrad_workspace", "ptt_linear_wgrad_f32",
-    "ptt_pack_weight_strided_f32", "ptt_linear_batched_f32", "ptt_softmax_rows_f32",
+    "ptt_pack_weight_strided_f32", "ptt_linear_batched_f32", "ptt_softmax_rows_f32", "ptt_layernorm_f32",
     "ptt_gather_rows_f32", "ptt_scatter_csr_i32", "ptt_scatter_rows_csr_f32",
     "ptt_pt_pair_input_f32", "ptt_pt_attn_train_fwd_f32", "ptt_pt_attn_train_bwd_f32", "ptt_linear_act_in_f32",
     "ptt_centres_ball_query_f32",
@@ -168,7 +168,7 @@ class AttnDesc(Structure):
                 ("Wd1p", c_void_p), ("Wd2p", c_void_p), ("bd2", c_void_p),
                 ("Wg1p", c_void_p), ("bg1", c_void_p), ("Wg2p", c_void_p), ("bg2", c_void_p),
                 ("res", c_void_p), ("attn", c_void_p),
-                ("B", c_int), ("N", c_int), ("k", c_int), ("D", c_int), ("order", c_void_p)]
+                ("B", c_int), ("N", c_int), ("k", c_int), ("D", c_int), ("order", c_void_p), ("heads", c_int)]
 
 
 _lib = None
@@ -239,6 +239,7 @@ def _declare(lib):
         "ptt_pack_weight_strided_f32": [vp, i, i, c_int64, c_int64, i, c_int64, vp, vp],
         "ptt_linear_batched_f32": [vp, i, i, i, c_int64, vp, c_int64, i, vp, vp, i, vp, i, c_int64, vp, i, c_int64, i, vp],
         "ptt_softmax_rows_f32": [vp, c_int64, i, i, f, vp],
+        "ptt_layernorm_f32": [vp, i, i, i, vp, vp, f, vp, i, vp, i, vp],
         "ptt_gather_rows_f32": [vp, vp, i, i, i, i, vp, vp],
         "ptt_scatter_csr_i32": [vp, i, i, i, vp, vp, vp],
         "ptt_scatter_rows_csr_f32": [vp, vp, vp, i, i, i, i, vp, vp],

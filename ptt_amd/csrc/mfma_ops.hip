@@ -1899,173 +1899,72 @@ struct AttnParams {
     long long* dbg;   // dev only: per-phase s_memtime stamps (PTT_DEBUG_STAMPS), NULL in production
 };
 
+// Multi-head form (MulHeadTransformerLayer, multitransformer.py:11-63): fc_delta is the same D x D layer; fc_gamma is ONE
+// hd x hd MLP (hd = D / HEADS) that every head shares, head h owning channels h*hd .. h*hd+hd-1. Output tile c = w + 4u
+// of a wave lies in head c / TPH (TPH = hd / 32 tiles per head) at local tile c % TPH, and reads only its head's hd input
+// channels. The wave keeps its tiles w, w+4, w+8, w+12 (the delta, gather, softmax and store code is the single-head
+// kernel's): with HEADS >= 4 the four tiles lie in four heads at the SAME local tile, so one weight fragment feeds all
+// four, each with its own A fragment; with HEADS = 2 two A and two weight fragments. 16 MFMAs per K-block either way,
+// hd / 8 K-blocks instead of D / 8.
+template <int D, int HEADS>
+__device__ __forceinline__ void gemm_heads(const float* Xs, int ldk, const float* Wp, int w, int lane, f32x16 (&acc)[1][4],
+                                           const f32x4 (&pre)[4]) {
+    static_assert(D == 512 && (HEADS == 2 || HEADS == 4 || HEADS == 8 || HEADS == 16), "4 waves x 4 column tiles of D = 512");
+    constexpr int HD = D / HEADS, TPH = HD / 32, NKB = HD / 8;
+    constexpr int NA = HEADS == 2 ? 2 : 4;      // distinct heads among the wave's tiles: A fragment of tile u = a[u / (4 / NA)]
+    constexpr int NB = HEADS == 2 ? 2 : 1;      // distinct local tiles: weight fragment of tile u = b[u % NB]
+    const int row = lane & 31, half = lane >> 5;
+    const float* arow[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) arow[i] = Xs + row * ldk + 4 * half + ((w + 4 * i * (4 / NA)) / TPH) * HD;
+    const __amdgpu_buffer_rsrc_t wr = weight_rsrc(Wp);
+    int wvoff[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) wvoff[i] = (((w + 4 * i) % TPH) * 64 + lane) * 16;
+    constexpr int wkstep = TPH * 1024;                     // bytes per K-block of the packed hd x hd weight
+    f32x4 bcur[NB], bnxt[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) { bcur[i] = pre[i]; bnxt[i] = bcur[i]; }
+    auto block = [&](int kb) {
+        f32x4 a[NA];
+#pragma unroll
+        for (int i = 0; i < NA; ++i) a[i] = *reinterpret_cast<const f32x4*>(arow[i] + kb * 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u / (4 / NA)][j], bcur[u % NB][j], acc[0][u], 0, 0, 0);
+    };
+    // gemm_core's PF = 1 form: one block of weights in flight, the last block peeled
+    for (int kb = 0; kb + 1 < NKB; ++kb) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) bnxt[i] = weight_load(wr, wvoff[i], (kb + 1) * wkstep);
+        block(kb);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) bcur[i] = bnxt[i];
+    }
+    block(NKB - 1);
+}
+
+// First K-block of a per-head fc_gamma weight for this wave's NB distinct local tiles (gemm_heads).
+template <int D, int HEADS>
+__device__ __forceinline__ void prefetch_first_block_heads(const float* Wp, int w, int lane, f32x4 (&pre)[4]) {
+    constexpr int TPH = D / HEADS / 32, NB = HEADS == 2 ? 2 : 1;
+    const f32x4* bp = reinterpret_cast<const f32x4*>(Wp) + lane;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) pre[i] = bp[(size_t)((w + 4 * i) % TPH) * 64];
+}
+
 template <int D>
 __global__ __launch_bounds__(256, 2) void pt_attn_pair_kernel(AttnParams p) {
-    constexpr int KNN = 16, NT = D / 32, CT = NT / 4, LDK = D + 4, NKB = D / 8;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Xs = smem;                                       // [32][LDK]
-    int* nb = reinterpret_cast<int*>(smem + 32 * LDK);      // [32] flat neighbour row (b*N + n)
-    constexpr int LDR = 12;                                 // [rel.x rel.y rel.z 1 | 0 0 0 0] + pad (stride = 4 mod 8)
-    float* relt = smem + 32 * LDK + 32;                     // [32][LDR]: the A operand of fc_delta[0]
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, half = lane >> 5;
-    const int slot0 = logical_block() * 2;                   // the tile's two point slots
-    const int npts = min(2, p.BN - slot0);
-    // the points behind the slots (ptt_spatial_order_f32: neighbours in space next to each other in launch order); both lie in
-    // the same cloud (N is even, the order permutes inside clouds)
-    const int s0 = slot0 < p.BN ? slot0 : p.BN - 1, s1 = slot0 + 1 < p.BN ? slot0 + 1 : p.BN - 1;
-    const int pt0 = p.order ? p.order[s0] : s0, pt1 = p.order ? p.order[s1] : s1;
-    f32x4 pre[CT];
-    prefetch_first_block_full<CT>(p.Wd1p, w, lane, pre);    // fc_delta[0]'s only weight block: requested first
-    stagger_second_slot(p.first_wave, p.stagger);
-    PTT_STAMP(0);
+    constexpr int HEADS = 1;
+#include "pt_attn_pair_body.h"
+}
 
-    if (t < 32) {
-        const int pt = (t >> 4) ? pt1 : pt0;
-        const int b = pt / p.N;
-        const int n = p.knn[(size_t)pt * KNN + (t & 15)];
-        const int flat = b * p.N + n;
-        nb[t] = n * (3 * D * (int)sizeof(float));      // byte offset of the neighbour's q|k|v row inside its cloud
-        f32x4 r4;
-        if (p.rel) {                                   // precomputed by the kNN kernel: no index -> xyz dependency
-            const float* rl = p.rel + ((size_t)pt * KNN + (t & 15)) * 3;
-            r4 = f32x4{rl[0], rl[1], rl[2], 1.f};
-        } else {
-            r4 = f32x4{p.xyz[(size_t)pt * 3 + 0] - p.xyz[(size_t)flat * 3 + 0],
-                       p.xyz[(size_t)pt * 3 + 1] - p.xyz[(size_t)flat * 3 + 1],
-                       p.xyz[(size_t)pt * 3 + 2] - p.xyz[(size_t)flat * 3 + 2], 1.f};
-        }
-        *reinterpret_cast<f32x4*>(relt + t * LDR) = r4;
-        *reinterpret_cast<f32x4*>(relt + t * LDR + 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    lds_barrier();
-
-    int cols[CT];
-#pragma unroll
-    for (int u = 0; u < CT; ++u) cols[u] = (w + 4 * u) * 32 + (lane & 31);
-
-    // fc_delta[0] + ReLU: h = relu([rel 1] . [W | b]^T) as ONE K-block of MFMAs (K = 4, zero-padded to 8) instead of
-    // ~500 vector-ALU instructions per wave — next to the other workgroup's MFMA stream those crawl (DESIGN.md lesson 8)
-    {
-        f32x16 h[1][CT];
-        zero_acc(h);
-        gemm_core<1, CT, CT, 4, 1>(relt, LDR, 1, reinterpret_cast<const f32x4*>(p.Wd1p), NT, w, lane, h, pre);
-        prefetch_first_block_full<CT>(p.Wd2p, w, lane, pre);    // fc_delta[2]'s first weight block
-#pragma unroll
-        for (int u = 0; u < CT; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Xs[tile_row(r, half) * LDK + cols[u]] = fmaxf(h[0][u][r], 0.f);
-    }
-    lds_barrier();
-
-    PTT_STAMP(1);
-    // ---- delta = fc_delta[2](h) ----
-    f32x16 delta[1][CT];
-    zero_acc(delta);
-    gemm_core<1, CT, CT, 4, PTT_PAIR_PF>(Xs, LDK, NKB, reinterpret_cast<const f32x4*>(p.Wd2p), NT, w, lane, delta, pre);
-    prefetch_first_block_full<CT>(p.Wg1p, w, lane, pre);    // next GEMM's first block: in flight across the epilogue
-#pragma unroll
-    for (int u = 0; u < CT; ++u) {
-        const float bb = p.bd2[cols[u]];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) delta[0][u][r] += bb;
-    }
-    PTT_STAMP(2);
-    // Gathers of neighbour k / v rows: raw buffer loads on a descriptor based at the cloud's first q|k|v row. The
-    // per-(row, lane) byte offset is ONE 32-bit VGPR per tile row; channel group and the k / v column block are
-    // immediates or an SGPR — a flat 64-bit address per load costs 3-4 vector-ALU instructions, 64 loads per phase.
-    const int cloud = pt0 / p.N;
-    const __amdgpu_buffer_rsrc_t rq = weight_rsrc(p.qkv + (size_t)cloud * p.N * 3 * D);
-    int nrow[16];  // byte offset of (neighbour row, this lane's first column) for each of this lane's 16 tile rows
-#pragma unroll
-    for (int r = 0; r < 16; ++r) nrow[r] = nb[tile_row(r, half)] + (w * 32 + (lane & 31)) * (int)sizeof(float);
-
-    lds_barrier();  // all waves done with h
-    // t = (q_i - k_j) + delta  -> X
-    {
-        const int pa = pt0, pb = (npts > 1) ? pt1 : pt0;
-#pragma unroll
-        for (int u = 0; u < CT; ++u) {
-            const float qa = p.qkv[(size_t)pa * 3 * D + cols[u]];
-            const float qb = p.qkv[(size_t)pb * 3 * D + cols[u]];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float kv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                    rq, nrow[r] + (D + u * 128) * (int)sizeof(float), 0, 0));
-                const float q = (r < 8) ? qa : qb;
-                Xs[tile_row(r, half) * LDK + cols[u]] = (q - kv) + delta[0][u][r];
-            }
-        }
-    }
-    lds_barrier();
-
-    PTT_STAMP(3);
-    // ---- g = relu(fc_gamma[0](t)) -> X ----
-    {
-        f32x16 acc[1][CT];
-        zero_acc(acc);
-        gemm_core<1, CT, CT, 4, PTT_PAIR_PF>(Xs, LDK, NKB, reinterpret_cast<const f32x4*>(p.Wg1p), NT, w, lane, acc, pre);
-        prefetch_first_block_full<CT>(p.Wg2p, w, lane, pre);
-        PTT_STAMP(4);
-        lds_barrier();
-#pragma unroll
-        for (int u = 0; u < CT; ++u) {
-            const float bb = p.bg1[cols[u]];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Xs[tile_row(r, half) * LDK + cols[u]] = fmaxf(acc[0][u][r] + bb, 0.f);
-        }
-        lds_barrier();
-    }
-
-    // ---- a = fc_gamma[2](g); softmax over the 16 neighbours; res = sum attn * (v + delta) ----
-    f32x16 acc[1][CT];
-    zero_acc(acc);
-    PTT_STAMP(5);
-    gemm_core<1, CT, CT, 4, PTT_PAIR_PF>(Xs, LDK, NKB, reinterpret_cast<const f32x4*>(p.Wg2p), NT, w, lane, acc, pre);
-    PTT_STAMP(6);
-    // softmax_j((a_j + b) / sqrt(D)) over the 16 neighbours of a point: the bias b is the same for every neighbour, so
-    // it cancels (fc_gamma[2].bias is never read); 1/sqrt(D) and log2(e) are one constant inside exp2; the weighted sum
-    // is normalised once at the end. Fewer vector-ALU instructions next to the other workgroup's MFMA stream.
-    const float kexp = 1.4426950408889634f / sqrtf((float)D);
-    // all 64 neighbour values of this lane are requested before any softmax arithmetic: one L2 round trip
-    // instead of eight (the gathers, not the math, were the length of this phase)
-    float vv[CT][16];
-#pragma unroll
-    for (int u = 0; u < CT; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            vv[u][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                rq, nrow[r] + u * 128 * (int)sizeof(float), 2 * D * (int)sizeof(float), 0));
-#pragma unroll
-    for (int u = 0; u < CT; ++u) {
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            float s[8];
-            float m = acc[0][u][pp * 8];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) m = fmaxf(m, acc[0][u][pp * 8 + r]);
-            m = max_halves(m);
-            float sum = 0.f, o = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int rr = pp * 8 + r;
-                s[r] = __builtin_amdgcn_exp2f((acc[0][u][rr] - m) * kexp);
-                sum += s[r];
-                o += s[r] * (vv[u][rr] + delta[0][u][rr]);
-            }
-            sum = add_halves(sum);
-            o = add_halves(o);
-            const float rsum = __builtin_amdgcn_rcpf(sum);
-            if (p.attn && pp < npts) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int row = tile_row(pp * 8 + r, half);  // = pp*16 + j
-                    p.attn[((size_t)(pp ? pt1 : pt0) * KNN + (row & 15)) * D + cols[u]] = s[r] * rsum;
-                }
-            }
-            if (half == 0 && pp < npts) p.res[(size_t)(pp ? pt1 : pt0) * D + cols[u]] = o * rsum;
-        }
-    }
-    PTT_STAMP(7);
+template <int HEADS>
+__global__ __launch_bounds__(256, 2) void pt_attn_pair_heads_kernel(AttnParams p) {
+    constexpr int D = 512;
+#include "pt_attn_pair_body.h"
 }
 
 // softmax(scale * x) along each row of a (rows, n) matrix, in place: one wave per row (the N x N scores of the dense
@@ -2090,9 +1989,68 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ X
     for (int c = lane; c < n; c += 64) x[c] *= inv;
 }
 
+// LayerNorm over the last dim of a (rows, C) matrix (nn.LayerNorm(C), multitransformer.py:59-60): one wave per row, fp32;
+// the mean first, then the variance of the centred values (two passes over registers, as torch does: no E[x^2] - mean^2
+// cancellation), y = (x - mean) / sqrt(var + eps) * weight + bias, then + residual when one is given. C <= 64 * LN_VPL.
+constexpr int LN_VPL = 16;
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ X, int rows, int C, int ldx,
+                                                             const float* __restrict__ weight, const float* __restrict__ bias,
+                                                             float eps, const float* __restrict__ R, int ldr,
+                                                             float* __restrict__ Y, int ldy) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* x = X + (size_t)r * ldx;
+    float v[LN_VPL];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_VPL; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = c < C ? x[c] : 0.f;
+        sum += v[i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const float mean = sum / (float)C;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_VPL; ++i) {
+        const float d = (lane + 64 * i) < C ? v[i] - mean : 0.f;
+        v[i] = d;
+        sq += d * d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    const float rstd = 1.0f / sqrtf(sq / (float)C + eps);
+    float* y = Y + (size_t)r * ldy;
+    const float* res = R ? R + (size_t)r * ldr : nullptr;
+#pragma unroll
+    for (int i = 0; i < LN_VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < C) {
+            float o = v[i] * rstd;
+            if (weight) o *= weight[c];
+            if (bias) o += bias[c];
+            if (res) o += res[c];
+            y[c] = o;
+        }
+    }
+}
+
 }  // namespace ptt
 
 using namespace ptt;
+
+extern "C" int ptt_layernorm_f32(const float* x, int rows, int C, int ldx, const float* weight, const float* bias, float eps,
+                                 const float* residual, int ldr, float* out, int ldo, ptt_stream_t stream) {
+    if (rows < 0 || C <= 0 || C > 64 * LN_VPL || ldx < C || ldo < C || (residual && ldr < C))
+        return fail(PTT_EINVAL, "ptt_layernorm_f32: rows=%d C=%d ldx=%d ldr=%d ldo=%d (C <= %d)", rows, C, ldx, ldr, ldo, 64 * LN_VPL);
+    if (rows == 0) return PTT_OK;
+    if (!x || !out) return fail(PTT_EINVAL, "ptt_layernorm_f32: null pointer");
+    hipLaunchKernelGGL(layernorm_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream), x, rows, C, ldx,
+                       weight, bias, eps, residual, ldr, out, ldo);
+    return check_launch("layernorm_rows_kernel");
+}
 
 extern "C" int ptt_softmax_rows_f32(float* X, int64_t rows, int n, int ld, float scale, ptt_stream_t stream) {
     if (rows < 0 || n <= 0 || ld < n) return fail(PTT_EINVAL, "ptt_softmax_rows_f32: rows=%lld n=%d ld=%d", (long long)rows, n, ld);
@@ -2520,10 +2478,25 @@ extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream)
     if ((d->N & 1) != 0)
         return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: N=%d must be even (a tile holds two points of one cloud)",
                     d->N);
+    const int heads = d->heads ? d->heads : 1;
     int lds = (32 * (512 + 4) + 32 + 32 * 12) * (int)sizeof(float);
     lds += dev_switches().pair_lds_pad;                               // dev: force 1 workgroup per CU
-    int rc = set_lds_limit(reinterpret_cast<const void*>(pt_attn_pair_kernel<512>), lds);
+    const void* kern;
+    switch (heads) {
+        case 1: kern = reinterpret_cast<const void*>(pt_attn_pair_kernel<512>); break;
+        case 2: kern = reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<2>); break;
+        case 4: kern = reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<4>); break;
+        case 8: kern = reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<8>); break;
+        default: return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d (1, 2, 4, 8 are instantiated)", d->heads);
+    }
+    int rc = set_lds_limit(kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL((pt_attn_pair_kernel<512>), dim3((p.BN + 1) / 2), dim3(256), lds, as_stream(stream), p);
-    return check_launch("pt_attn_pair_kernel");
+    const dim3 grid((p.BN + 1) / 2);
+    switch (heads) {
+        case 1: hipLaunchKernelGGL((pt_attn_pair_kernel<512>), grid, dim3(256), lds, as_stream(stream), p); break;
+        case 2: hipLaunchKernelGGL((pt_attn_pair_heads_kernel<2>), grid, dim3(256), lds, as_stream(stream), p); break;
+        case 4: hipLaunchKernelGGL((pt_attn_pair_heads_kernel<4>), grid, dim3(256), lds, as_stream(stream), p); break;
+        default: hipLaunchKernelGGL((pt_attn_pair_heads_kernel<8>), grid, dim3(256), lds, as_stream(stream), p); break;
+    }
+    return check_launch(heads == 1 ? "pt_attn_pair_kernel" : "pt_attn_pair_heads_kernel");
 }

@@ -1,3 +1,3 @@
-from .layer_utils import index_points, square_distance
+from .layer_utils import get_clones, index_points, square_distance
 
-__all__ = ["square_distance", "index_points"]
+__all__ = ["get_clones", "square_distance", "index_points"]

@@ -1,9 +1,17 @@
-"""Mirror of ptt/models/model_utils/layer_utils.py:12-40 (square_distance, index_points).
+"""Mirror of ptt/models/model_utils/layer_utils.py:8-40 (get_clones, square_distance, index_points).
 
 Plain torch; used by the training-mode (unfused) transformer path. The fused inference path
 replaces both with ptt_knn_f32 and in-kernel gathers.
 """
+import copy
+
 import torch
+import torch.nn as nn
+
+
+def get_clones(module, N):
+    """N independent deep copies of `module` in an nn.ModuleList (layer_utils.py:8-9): MulTransformerBlock's layers."""
+    return nn.ModuleList([copy.deepcopy(module) for _ in range(N)])
 
 
 def square_distance(src, dst):

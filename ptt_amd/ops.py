@@ -611,11 +611,14 @@ def spatial_order(xyz):
     return order
 
 
-def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_model, want_attn=True, rel=None, order=None):
+def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_model, want_attn=True, rel=None, order=None,
+                 heads=1):
     """Fused per-(point,neighbour) part of TransformerBlock.forward (variants.py:158-163).
     wd1p = pack_delta0(fc_delta[0].weight, fc_delta[0].bias); the other weights from pack_weight. order: spatial_order(xyz) or
     None — which point every launch slot works on (the results do not depend on it).
-    Returns (res (B,N,D), attn (B,N,k,D) | None)."""
+    heads > 1 (2, 4, 8): MulHeadTransformerLayer's attention (multitransformer.py:46-56) — wg1p / wg2p are the packed
+    hd x hd fc_gamma weights every head shares (hd = d_model / heads), bg1 is fc_gamma[0].bias repeated `heads` times.
+    Returns (res (B,N,D), attn | None): attn (B,N,k,D), or (B*heads,N,k,hd) when heads > 1."""
     _chk(xyz, "xyz", torch.float32, 3)
     _chk(knn_idx, "knn_idx", torch.int32, 3)
     _chk(qkv, "qkv", torch.float32, 3)
@@ -623,7 +626,8 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
     k = knn_idx.shape[2]
     D = int(d_model)
     res = torch.empty((B, N, D), dtype=torch.float32, device=xyz.device)
-    attn = torch.empty((B, N, k, D), dtype=torch.float32, device=xyz.device) if want_attn else None
+    ashape = (B, N, k, D) if heads == 1 else (B * heads, N, k, D // heads)
+    attn = torch.empty(ashape, dtype=torch.float32, device=xyz.device) if want_attn else None
     d = AttnDesc()
     d.xyz, d.knn, d.qkv = xyz.data_ptr(), knn_idx.data_ptr(), qkv.data_ptr()
     d.rel = rel.data_ptr() if rel is not None else None
@@ -631,7 +635,7 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
     d.Wg1p, d.bg1, d.Wg2p, d.bg2 = wg1p.data_ptr(), bg1.data_ptr(), wg2p.data_ptr(), bg2.data_ptr()
     d.res = res.data_ptr()
     d.attn = attn.data_ptr() if attn is not None else None
-    d.B, d.N, d.k, d.D = B, N, k, D
+    d.B, d.N, d.k, d.D, d.heads = B, N, k, D, int(heads)
     if order is not None:
         _chk(order, "order", torch.int32, 2)
         if tuple(order.shape) != (B, N):
@@ -640,6 +644,30 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
     with torch.cuda.device(xyz.device), _timed('ptt_pt_attn_pair_f32'):
         _lib.check(_lib.lib().ptt_pt_attn_pair_f32(ctypes.byref(d), _stream()), "ptt_pt_attn_pair_f32")
     return res, attn
+
+
+def layernorm(x, weight, bias, eps, residual=None, out=None):
+    """nn.LayerNorm over the last dim of x (..., C) (+ residual, added after the affine), ptt_layernorm_f32. out may be x."""
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError("x must be a float32 device tensor")
+    C = x.shape[-1]
+    x2 = x.reshape(-1, C)
+    if x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    o2 = out.view(-1, C)
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(-1, C)
+        if r2.stride(1) != 1:
+            r2 = r2.contiguous()
+    rows = x2.shape[0]
+    with torch.cuda.device(x.device), _timed('ptt_layernorm_f32'):
+        _lib.check(_lib.lib().ptt_layernorm_f32(_ptr(x2), rows, C, x2.stride(0) if rows > 1 else C, _ptr(weight), _ptr(bias),
+                                                float(eps), _ptr(r2), (r2.stride(0) if (r2 is not None and rows > 1) else C),
+                                                _ptr(o2), o2.stride(0) if rows > 1 else C, _stream()), "ptt_layernorm_f32")
+    return out
 
 
 # --------------------------------------------------------------------------- N4: tracking-loop pre/post-processing
