@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 24
+#define PTT_ABI_VERSION 25
 
 enum {
     PTT_OK = 0,
@@ -933,6 +933,32 @@ int ptt_rows_gemm_rsum16_f32(const float* X, int rows, int K, int ldx, const flo
                              float* out, int ldo, float* plain, int ldp, float* gsum, int ldg, ptt_stream_t stream);
 int ptt_scatter_rows_csr_sub_f32(const float* g, const int32_t* order, const int32_t* start, int B, int N, int E, int C,
                                  const float* minuend, float* out, ptt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * MulTransformerBlock in TRAINING mode (transformer_block/multitransformer.py:37-63 under autograd), ABI 25:
+ *   ptt_layernorm_train_fwd_f32  out = LayerNorm_C(x) * weight + bias (+ residual) over the rows of a (rows, C) matrix as
+ *                                ptt_layernorm_f32 (one wave per row, biased variance of the centred values, eps inside the root),
+ *                                and the row's mean and rstd = 1 / sqrt(var + eps) (float32, `rows` each) for the backward pass.
+ *                                C <= 1024; weight and bias are required.
+ *   ptt_layernorm_bwd_f32        with g = dy * weight, xhat = (x - mean) * rstd:
+ *                                  dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))      one wave per row
+ *                                  dbias = sum_rows dy, dweight = sum_rows dy * xhat          fixed 32-row chunks -> float64 partial
+ *                                slabs in the workspace -> a finish in chunk order: no atomics, bit-reproducible. The residual's
+ *                                gradient is dy itself. workspace: ptt_layernorm_bwd_workspace(rows, C) bytes.
+ *   ptt_rows_gemm_rsum16_heads_f32   ptt_rows_gemm_rsum16_f32 for fc_gamma[0] of a block with D / hd heads: X (rows, D) is head-major
+ *                                in the channel axis (channel c = h * hd + d), Wpacked ONE hd x hd weight all heads share, and
+ *                                plain[:, h hd : (h + 1) hd] = X[:, h hd : (h + 1) hd] @ W^T; out and gsum as the single-head form.
+ *                                ptt_rows_gemm_rsum16_heads_supported: D % hd == 0, hd % 128 == 0, D % 128 == 0, rows % 16 == 0.
+ * ------------------------------------------------------------------------------- */
+int ptt_layernorm_train_fwd_f32(const float* x, int rows, int C, int ldx, const float* weight, const float* bias, float eps,
+                                const float* residual, int ldr, float* out, int ldo, float* mean, float* rstd, ptt_stream_t stream);
+size_t ptt_layernorm_bwd_workspace(int rows, int C);
+int ptt_layernorm_bwd_f32(const float* dy, int ldg, const float* x, int ldx, const float* mean, const float* rstd, const float* weight,
+                          int rows, int C, float* dx, int ldd, float* dweight, float* dbias, void* workspace, size_t workspace_bytes,
+                          ptt_stream_t stream);
+int ptt_rows_gemm_rsum16_heads_supported(int rows, int D, int hd, int ldx);
+int ptt_rows_gemm_rsum16_heads_f32(const float* X, int rows, int D, int hd, int ldx, const float* Wpacked, const float* residual, int ldr,
+                                   float* out, int ldo, float* plain, int ldp, float* gsum, int ldg, ptt_stream_t stream);
 
 #ifdef __cplusplus
 }

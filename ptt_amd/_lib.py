@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libptt_hip.so")
 
 PTT_SA_MAX_LAYERS = 4
-ABI_VERSION = 24            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
+ABI_VERSION = 25            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
 
 # every symbol include/ptt_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -45,6 +45,8 @@ EXPORTS = [
     "ptt_linear_wgrad_partials_f32", "ptt_linear_wgrad2_partials_f32", "ptt_colsum_partials_f32", "ptt_grad_finish_f32",
     "ptt_rows_gemm_rsum16_supported", "ptt_rows_gemm_rsum16_f32", "ptt_scatter_rows_csr_sub_f32",
     "ptt_unit_rows_f32", "ptt_cos_bwd_rows_f32", "ptt_track_select_update", "ptt_sa_z0_bnbwd_workspace", "ptt_sa_compact_workspace", "ptt_sa_z0_bnbwd_f32",
+    "ptt_layernorm_train_fwd_f32", "ptt_layernorm_bwd_workspace", "ptt_layernorm_bwd_f32",
+    "ptt_rows_gemm_rsum16_heads_supported", "ptt_rows_gemm_rsum16_heads_f32",
 ]
 PTT_MAX_SEGMENTS = 4
 
@@ -259,6 +261,10 @@ def _declare(lib):
         "ptt_grad_finish_f32": [vp, vp, vp, i, vp, vp],
         "ptt_rows_gemm_rsum16_supported": [i, i, i, i],
         "ptt_rows_gemm_rsum16_f32": [vp, i, i, i, vp, i, vp, i, vp, i, vp, i, vp, i, vp],
+        "ptt_rows_gemm_rsum16_heads_supported": [i, i, i, i],
+        "ptt_rows_gemm_rsum16_heads_f32": [vp, i, i, i, i, vp, vp, i, vp, i, vp, i, vp, i, vp],
+        "ptt_layernorm_train_fwd_f32": [vp, i, i, i, vp, vp, f, vp, i, vp, i, vp, vp, vp],
+        "ptt_layernorm_bwd_f32": [vp, i, vp, i, vp, vp, vp, i, i, vp, i, vp, vp, vp, c_size_t, vp],
         "ptt_scatter_rows_csr_sub_f32": [vp, vp, vp, i, i, i, i, vp, vp, vp],
         "ptt_rows_gemm_bnbwd_f32": [vp, i, i, i, vp, i, vp, i, vp, vp, vp, vp, vp, i, vp, c_size_t, vp],
         "ptt_bn_bwd_from_partials_f32": [vp, i, vp, i, vp, i, vp, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp],
@@ -309,6 +315,8 @@ def _declare(lib):
     lib.ptt_sa_compact_workspace.argtypes = [i, i]
     lib.ptt_adam_chunk_elems.restype = c_int
     lib.ptt_adam_chunk_elems.argtypes = []
+    lib.ptt_layernorm_bwd_workspace.restype = c_size_t
+    lib.ptt_layernorm_bwd_workspace.argtypes = [i, i]
     lib.ptt_colsum_workspace.restype = c_size_t
     lib.ptt_colsum_workspace.argtypes = [i, i]
     lib.ptt_linear_wgrad2_workspace.restype = c_size_t

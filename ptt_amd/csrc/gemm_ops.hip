@@ -95,6 +95,9 @@ struct RowsGemmParams {
     // GS instantiations (with `residual`): the product is ALSO written without the residual (plain), and summed per group of 16
     // consecutive rows and column (gsum)
     float* gsum; float* plain; int ldgs, ldpl;
+    // HD instantiations (per-head shared weight): the N = K columns fall into K / hd heads, Wp is ONE packed hd x hd weight, and the
+    // output columns [h hd, (h + 1) hd) are the product of the SAME columns of X with it (NT = hd / 32, nchunks = hd / KC)
+    int hd;
 };
 
 // WR x WC waves (WR * WC = 4): wave (wr, wc) owns row tiles wr*RT .. wr*RT+RT-1 of the workgroup's 32*RT*WR rows and the
@@ -106,8 +109,11 @@ struct RowsGemmParams {
 #endif
 // BNB: the statistics are the BatchNorm backward sums of the producing layer (p.bz ...), not those of the output
 // GS 16: the launch also sums its outputs (after the residual) over groups of 16 consecutive rows (ptt_rows_gemm_rsum16_f32)
-template <int WR, int RT, int CT, int KC, bool STATS, bool ACT, int EXP = 0, bool BNB = false, int POOL = 0, int AIN = 0, int GS = 0>
+// HD: per-head shared weight (MulTransformerBlock's fc_gamma: one hd x hd MLP for every head, heads head-major in the channel axis) —
+// a workgroup's column group lies inside one head, its K loop runs over that head's hd columns of X only
+template <int WR, int RT, int CT, int KC, bool STATS, bool ACT, int EXP = 0, bool BNB = false, int POOL = 0, int AIN = 0, int GS = 0, bool HD = false>
 __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
+    static_assert(!HD || GS == 16, "the per-head form is instantiated for the group-sum launch only");
     static_assert(GS == 0 || (GS == 16 && !STATS && !ACT && !BNB && POOL == 0 && AIN == 0), "group sums: a plain GEMM with a residual");
     static_assert(!BNB || (STATS && !ACT), "the backward-sums epilogue is a statistics epilogue of a plain input gradient");
     static_assert(AIN == 0 || AIN == 2 || AIN == 16 || AIN == 32 || AIN == 64, "A-operand form");
@@ -134,7 +140,11 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
                                                                          ((p.rows - 1) * p.ldx + p.K) * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = g_rsrc(p.Wp), ro = g_rsrc(p.out);
     const int ct0 = cg * (WC * CT) + wc;
-    const int wvoff = (ct0 * 64 + lane) * 16;                   // this lane's byte offset inside a K-block row of fragments
+    // HD: the head of this workgroup's columns; its first input channel (bytes) and its column tiles inside the shared weight
+    const int head = HD ? (cg * (WC * CT * 32)) / p.hd : 0;
+    const int xk0 = HD ? head * p.hd * 4 : 0;
+    const int ct0w = HD ? ct0 - head * (p.hd >> 5) : ct0;
+    const int wvoff = (ct0w * 64 + lane) * 16;                  // this lane's byte offset inside a K-block row of fragments
     const int wkstep = p.NT * 1024;                             // bytes per K-block of the packed weights
     // staging slots of this thread: slot i = float4 (row r0 + i * RSTEP, channel quad q) of the unit's [TR][KC] block
     constexpr int RSTEP = 256 / QPR;
@@ -181,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
         const int tcl = tile < p.ntiles ? tile : p.ntiles;
         const int tb_off = tcl * tile_bytes + slot_off;
 #pragma unroll
-        for (int i = 0; i < SLOTS; ++i) st[i] = g_load4(rx, tb_off + i * (RSTEP * ldx4), c * (KC * 4));
+        for (int i = 0; i < SLOTS; ++i) st[i] = g_load4(rx, tb_off + i * (RSTEP * ldx4), c * (KC * 4) + xk0);
         if (ACT || AIN) {
             ta = *reinterpret_cast<const g32x4*>(p.in_a + c * KC + 4 * q);
             tb = *reinterpret_cast<const g32x4*>(p.in_b + c * KC + 4 * q);
@@ -672,7 +682,7 @@ extern "C" int ptt_rows_gemm_stat_chunks(int rows, int K, int N) {
 
 struct BnBwdArgs { const float* z; int ldz; const float* mean; const float* invstd; const float* a; const float* b; };
 struct PoolArgs { float* pmax; float* pmin; int32_t* amax; int32_t* amin; int ns; };
-struct GroupSumArgs { float* gsum; int ldgs; float* plain; int ldpl; };
+struct GroupSumArgs { float* gsum; int ldgs; float* plain; int ldpl; int hd; };      // hd > 0: the per-head shared-weight form
 static int rows_gemm_launch(const float* X, int rows, int K, int ldx, const float* in_scale, const float* in_shift,
                             const float* Wpacked, int N, const float* bias, int relu, const float* residual, int ldr,
                             const float* mask, int ldm, float* out, int ldo, double* stats, size_t stats_elems, ptt_stream_t stream,
@@ -695,8 +705,30 @@ extern "C" int ptt_rows_gemm_rsum16_f32(const float* X, int rows, int K, int ldx
     if ((long long)rows * ldp >= (1LL << 31)) return fail(PTT_EUNSUPPORTED, "ptt_rows_gemm_rsum16_f32: rows * ldp >= 2^31");
     if (!ptt_rows_gemm_rsum16_supported(rows, K, N, ldx))
         return fail(PTT_EUNSUPPORTED, "ptt_rows_gemm_rsum16_f32: rows=%d K=%d N=%d (whole groups of 16 rows, K %% 128 == 0, N %% 128 == 0)", rows, K, N);
-    const GroupSumArgs gs{gsum, ldg, plain, ldp};
+    const GroupSumArgs gs{gsum, ldg, plain, ldp, 0};
     return rows_gemm_launch(X, rows, K, ldx, nullptr, nullptr, Wpacked, N, nullptr, 0, residual, ldr, nullptr, 0, out, ldo, nullptr, 0, stream,
+                            nullptr, nullptr, nullptr, &gs);
+}
+
+// The per-head form: X (rows, D) holds D / hd heads of hd channels each (head-major), Wpacked is ONE hd x hd weight shared by the heads:
+// plain[:, h hd : (h + 1) hd] = X[:, h hd : (h + 1) hd] @ W^T — MulTransformerBlock's fc_gamma[0] input gradient, with the residual and the
+// group sums of ptt_rows_gemm_rsum16_f32. 128 output columns per workgroup unless a head spans whole 256-column groups.
+extern "C" int ptt_rows_gemm_rsum16_heads_supported(int rows, int D, int hd, int ldx) {
+    if (hd <= 0 || D <= 0 || D % hd || hd % 128) return 0;
+    return ptt_rows_gemm_rsum16_supported(rows, D, D, ldx);
+}
+
+extern "C" int ptt_rows_gemm_rsum16_heads_f32(const float* X, int rows, int D, int hd, int ldx, const float* Wpacked, const float* residual,
+                                              int ldr, float* out, int ldo, float* plain, int ldp, float* gsum, int ldg,
+                                              ptt_stream_t stream) {
+    if (!residual || !plain || !gsum || ldp < D || ldg < D)
+        return fail(PTT_EINVAL, "ptt_rows_gemm_rsum16_heads_f32: null pointer or ldp / ldg < D");
+    if ((long long)rows * ldp >= (1LL << 31)) return fail(PTT_EUNSUPPORTED, "ptt_rows_gemm_rsum16_heads_f32: rows * ldp >= 2^31");
+    if (!ptt_rows_gemm_rsum16_heads_supported(rows, D, hd, ldx))
+        return fail(PTT_EUNSUPPORTED, "ptt_rows_gemm_rsum16_heads_f32: rows=%d D=%d hd=%d (whole groups of 16 rows, D %% hd == 0, hd %% 128 == 0)",
+                    rows, D, hd);
+    const GroupSumArgs gs{gsum, ldg, plain, ldp, hd};
+    return rows_gemm_launch(X, rows, D, ldx, nullptr, nullptr, Wpacked, D, nullptr, 0, residual, ldr, nullptr, 0, out, ldo, nullptr, 0, stream,
                             nullptr, nullptr, nullptr, &gs);
 }
 
@@ -788,7 +820,16 @@ static int rows_gemm_launch(const float* X, int rows, int K, int ldx, const floa
     if ((reinterpret_cast<uintptr_t>(X) & 15) || (in_scale && ((reinterpret_cast<uintptr_t>(in_scale) | reinterpret_cast<uintptr_t>(in_shift)) & 15)))
         return fail(PTT_EINVAL, "ptt_rows_gemm_f32: X / in_scale / in_shift must be 16-byte aligned");
     if ((in_scale == nullptr) != (in_shift == nullptr)) return fail(PTT_EINVAL, "ptt_rows_gemm_f32: in_scale and in_shift go together");
-    const RowsGemmGeom g = rows_gemm_geom(rows, K, N);
+    RowsGemmGeom g = rows_gemm_geom(rows, K, N);
+    if (gs && gs->hd > 0 && g.CT == 2 && gs->hd % 256) {      // a 256-column group would straddle two heads: 128 columns per workgroup
+        g.CT = 1;
+        g.ncg = N / 128;
+        int cap = 2 * cu_count() / g.ncg;
+        if (cap >= 8) cap &= ~7;
+        if (cap < 1) cap = 1;
+        g.G = g.ntiles < cap ? g.ntiles : cap;
+        g.chunks = g.G * g.WR;
+    }
     if (bn && (!stats || bias || residual || mask || in_scale)) return fail(PTT_EINVAL, "ptt_rows_gemm_bnbwd_f32: plain input gradient only");
     if (pool && (!stats || bias || residual || mask || bn || !in_scale || relu || !pool->pmax || !pool->pmin || !pool->amax || !pool->amin ||
                  rows % pool->ns))
@@ -815,6 +856,8 @@ static int rows_gemm_launch(const float* X, int rows, int K, int ldx, const floa
         p.tg = ain->g; p.ldtg = ain->ldg; p.targ = ain->arg; p.a_out = ain->dz_out; p.lda_out = ain->ldd;
     }
     p.gsum = gs ? gs->gsum : nullptr; p.plain = gs ? gs->plain : nullptr; p.ldgs = gs ? gs->ldgs : 0; p.ldpl = gs ? gs->ldpl : 0;
+    p.hd = gs ? gs->hd : 0;
+    if (p.hd > 0) { p.NT = p.hd / 32; p.nchunks = p.hd / g.KC; }
     const int lds = 2 * g.TR * (g.KC + 4) * (int)sizeof(float);
     const dim3 grid(g.G * g.ncg);
     hipStream_t s = as_stream(stream);
@@ -826,6 +869,16 @@ static int rows_gemm_launch(const float* X, int rows, int K, int ldx, const floa
         if (g.WR == 1 && g.RT == 2 && g.CT == CT_ && g.KC == 128) {                                                     \
             if ((rc = set_lds_limit(reinterpret_cast<const void*>(rows_gemm_kernel<1, 2, CT_, 128, false, false, 0, false, 0, 0, 16>), lds))) return rc; \
             hipLaunchKernelGGL((rows_gemm_kernel<1, 2, CT_, 128, false, false, 0, false, 0, 0, 16>), grid, dim3(256), lds, s, p); \
+        }
+        if (gs->hd > 0) {
+#define PTT_RG_GSH(CT_)                                                                                                 \
+            if (g.WR == 1 && g.RT == 2 && g.CT == CT_ && g.KC == 128) {                                                 \
+                if ((rc = set_lds_limit(reinterpret_cast<const void*>(rows_gemm_kernel<1, 2, CT_, 128, false, false, 0, false, 0, 0, 16, true>), lds))) return rc; \
+                hipLaunchKernelGGL((rows_gemm_kernel<1, 2, CT_, 128, false, false, 0, false, 0, 0, 16, true>), grid, dim3(256), lds, s, p); \
+            }
+            PTT_RG_GSH(2) PTT_RG_GSH(1)
+#undef PTT_RG_GSH
+            return check_launch("rows_gemm_kernel(rsum16, heads)");
         }
         PTT_RG_GS(2) PTT_RG_GS(1)
 #undef PTT_RG_GS

@@ -1393,12 +1393,148 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
 }
 
 void launch_wgrad_finish(const float* partial, int nchunks, size_t n, int accumulate, float* dW, hipStream_t s) {
-    const int out = nchunks > 1024 ? 4 : nchunks > 256 ? 8 : 32;       // a function of the chunk count only: fixed summation tree
+    // a function of the chunk count only: fixed summation tree — and the SAME function as ops.GradFinishPlan._outputs_per_group, so
+    // that a gradient finished here and the same partials finished by ptt_grad_finish_f32 (one job, chunk k in group k % G, groups
+    // folded in order) are the same sum, bit for bit
+    const int out = nchunks > 1024 ? 4 : nchunks > 256 ? 8 : nchunks > 64 ? 16 : nchunks > 8 ? 32 : nchunks > 2 ? 64 : 256;
     size_t fgrid = (n + out - 1) / out;
     if (fgrid > 4096) fgrid = 4096;
-    if (out == 4) hipLaunchKernelGGL(wgrad_finish_kernel<4>, dim3((unsigned)fgrid), dim3(256), 0, s, partial, nchunks, n, accumulate, dW);
-    else if (out == 8) hipLaunchKernelGGL(wgrad_finish_kernel<8>, dim3((unsigned)fgrid), dim3(256), 0, s, partial, nchunks, n, accumulate, dW);
-    else hipLaunchKernelGGL(wgrad_finish_kernel<32>, dim3((unsigned)fgrid), dim3(256), 0, s, partial, nchunks, n, accumulate, dW);
+#define PTT_WF(O) if (out == O) hipLaunchKernelGGL(wgrad_finish_kernel<O>, dim3((unsigned)fgrid), dim3(256), 0, s, partial, nchunks, n, accumulate, dW);
+    PTT_WF(4) PTT_WF(8) PTT_WF(16) PTT_WF(32) PTT_WF(64) PTT_WF(256)
+#undef PTT_WF
+}
+
+// ------------------------------------------------------------------------------------------
+// nn.LayerNorm in TRAINING mode over the rows of a (rows, C) matrix (multitransformer.py:59-60: norm1, norm2), C <= 64 * LNT_VPL.
+// Forward: one wave per row, lane l holds channels l, l + 64, ...; the mean, then the (biased) variance of the centred values, as
+// ptt_layernorm_f32 does — and the row's mean and 1 / sqrt(var + eps) written out for the backward pass.
+// Backward, with g = dy * w and xhat = (x - mean) * rstd:
+//     dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))                 (one wave per row, wave reductions)
+//     db = sum_rows dy,  dw = sum_rows dy * xhat                            (column sums over the rows)
+// A workgroup owns LNB_ROWS consecutive rows, a wave every fourth of them: each lane sums its channels' terms over its wave's rows in
+// float32 (LNB_ROWS / 4 terms), the four waves are added in wave order in float64 and go out as partial[chunk][2][C]
+// (0: db, 1: dw), which col_stats_finish2_kernel<1> adds in its fixed order: no atomics, bit-reproducible.
+// ------------------------------------------------------------------------------------------
+constexpr int LNT_VPL = 16, LNB_ROWS = 32;
+
+__device__ __forceinline__ float ln_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void layernorm_train_fwd_kernel(const float* __restrict__ X, int rows, int C, int ldx,
+                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                  float eps, const float* __restrict__ R, int ldr,
+                                                                  float* __restrict__ Y, int ldy, float* __restrict__ mean_out,
+                                                                  float* __restrict__ rstd_out) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* x = X + (size_t)r * ldx;
+    float v[LNT_VPL];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < LNT_VPL; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = c < C ? x[c] : 0.f;
+        sum += v[i];
+    }
+    // the float32 sum of a row with a large common offset carries a rounding error of the offset's size: centre on it first, then
+    // remove the mean of the centred values (small, so its own rounding does not matter) — the mean twice, as a compensated sum
+    const float mean0 = ln_wave_sum(sum) / (float)C;
+    float rest = 0.f;
+#pragma unroll
+    for (int i = 0; i < LNT_VPL; ++i) {
+        v[i] = (lane + 64 * i) < C ? v[i] - mean0 : 0.f;
+        rest += v[i];
+    }
+    const float corr = ln_wave_sum(rest) / (float)C;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < LNT_VPL; ++i) {
+        const float d = (lane + 64 * i) < C ? v[i] - corr : 0.f;
+        v[i] = d;
+        sq += d * d;
+    }
+    const float rstd = 1.0f / sqrtf(ln_wave_sum(sq) / (float)C + eps);
+    if (lane == 0) { mean_out[r] = mean0 + corr; rstd_out[r] = rstd; }
+    float* y = Y + (size_t)r * ldy;
+    const float* res = R ? R + (size_t)r * ldr : nullptr;
+#pragma unroll
+    for (int i = 0; i < LNT_VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < C) {
+            float o = v[i] * rstd * weight[c] + bias[c];
+            if (res) o += res[c];
+            y[c] = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dY, int ldg, const float* __restrict__ X, int ldx,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ weight, int rows, int C,
+                                                            float* __restrict__ dX, int ldd, double* __restrict__ partial) {
+    __shared__ float red[2][4][64 * LNT_VPL];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * LNB_ROWS, r1 = min(rows, r0 + LNB_ROWS);
+    float wv[LNT_VPL], sb[LNT_VPL], sw[LNT_VPL];
+#pragma unroll
+    for (int i = 0; i < LNT_VPL; ++i) {
+        const int c = lane + 64 * i;
+        wv[i] = c < C ? weight[c] : 0.f;
+        sb[i] = 0.f; sw[i] = 0.f;
+    }
+    const float invC = 1.0f / (float)C;
+    for (int r = r0 + w; r < r1; r += 4) {                      // wave-uniform: every lane of a wave works on the same row
+        const float* dy = dY + (size_t)r * ldg;
+        const float* x = X + (size_t)r * ldx;
+        const float mu = mean[r], rs = rstd[r];
+        float g[LNT_VPL], xh[LNT_VPL];
+        // the stored mean is a float32: next to a large common offset of the row it is off by up to half an ulp OF THE OFFSET, which
+        // xhat would inherit — the mean of the values centred on it is that remainder (as the forward pass forms it)
+        float rest = 0.f;
+#pragma unroll
+        for (int i = 0; i < LNT_VPL; ++i) {
+            const int c = lane + 64 * i;
+            xh[i] = c < C ? x[c] - mu : 0.f;
+            rest += xh[i];
+        }
+        const float corr = ln_wave_sum(rest) * invC;
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < LNT_VPL; ++i) {
+            const int c = lane + 64 * i;
+            const bool in = c < C;
+            const float d = in ? dy[c] : 0.f;
+            xh[i] = in ? (xh[i] - corr) * rs : 0.f;
+            g[i] = d * wv[i];
+            sb[i] += d;
+            sw[i] = __builtin_fmaf(d, xh[i], sw[i]);
+            s1 += g[i];
+            s2 = __builtin_fmaf(g[i], xh[i], s2);
+        }
+        const float m1 = ln_wave_sum(s1) * invC, m2 = ln_wave_sum(s2) * invC;
+        float* dx = dX + (size_t)r * ldd;
+#pragma unroll
+        for (int i = 0; i < LNT_VPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < C) dx[c] = rs * (g[i] - m1 - xh[i] * m2);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < LNT_VPL; ++i) {
+        red[0][w][lane + 64 * i] = sb[i];
+        red[1][w][lane + 64 * i] = sw[i];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const double b = (((double)red[0][0][c] + (double)red[0][1][c]) + (double)red[0][2][c]) + (double)red[0][3][c];
+        const double a = (((double)red[1][0][c] + (double)red[1][1][c]) + (double)red[1][2][c]) + (double)red[1][3][c];
+        partial[((size_t)blockIdx.x * 2 + 0) * C + c] = b;
+        partial[((size_t)blockIdx.x * 2 + 1) * C + c] = a;
+    }
 }
 
 static inline int ew_grid(size_t total) {
@@ -2137,4 +2273,38 @@ extern "C" int ptt_bn_bwd_pooled_consts_f32(const float* dPooled, int ldp, const
     hipLaunchKernelGGL(bn_bwd_consts_kernel, dim3(C), dim3(256), 0, s, static_cast<const double*>(ws), nch, C, R, invstd, gamma, dbeta, dgamma,
                        k1, c0, c1);
     return check_launch("ptt_bn_bwd_pooled_consts_f32");
+}
+
+// ---- nn.LayerNorm in training mode (the kernels' header comment above has the formulas) ----
+extern "C" int ptt_layernorm_train_fwd_f32(const float* x, int rows, int C, int ldx, const float* weight, const float* bias, float eps,
+                                           const float* residual, int ldr, float* out, int ldo, float* mean, float* rstd,
+                                           ptt_stream_t stream) {
+    if (rows < 0 || C <= 0 || C > 64 * LNT_VPL || ldx < C || ldo < C || (residual && ldr < C))
+        return fail(PTT_EINVAL, "ptt_layernorm_train_fwd_f32: rows=%d C=%d ldx=%d ldr=%d ldo=%d (C <= %d)", rows, C, ldx, ldr, ldo, 64 * LNT_VPL);
+    if (rows == 0) return PTT_OK;
+    if (!x || !out || !weight || !bias || !mean || !rstd) return fail(PTT_EINVAL, "ptt_layernorm_train_fwd_f32: null pointer");
+    hipLaunchKernelGGL(layernorm_train_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream), x, rows, C, ldx,
+                       weight, bias, eps, residual, ldr, out, ldo, mean, rstd);
+    return check_launch("layernorm_train_fwd_kernel");
+}
+
+extern "C" size_t ptt_layernorm_bwd_workspace(int rows, int C) {
+    if (rows <= 0 || C <= 0) return 0;
+    return (size_t)((rows + LNB_ROWS - 1) / LNB_ROWS) * 2 * (size_t)C * sizeof(double);
+}
+
+extern "C" int ptt_layernorm_bwd_f32(const float* dy, int ldg, const float* x, int ldx, const float* mean, const float* rstd,
+                                     const float* weight, int rows, int C, float* dx, int ldd, float* dweight, float* dbias,
+                                     void* ws, size_t ws_bytes, ptt_stream_t stream) {
+    if (rows <= 0 || C <= 0 || C > 64 * LNT_VPL || ldg < C || ldx < C || ldd < C)
+        return fail(PTT_EINVAL, "ptt_layernorm_bwd_f32: rows=%d C=%d ldg=%d ldx=%d ldd=%d (C <= %d)", rows, C, ldg, ldx, ldd, 64 * LNT_VPL);
+    if (!dy || !x || !mean || !rstd || !weight || !dx || !dweight || !dbias) return fail(PTT_EINVAL, "ptt_layernorm_bwd_f32: null pointer");
+    if (!ws || ws_bytes < ptt_layernorm_bwd_workspace(rows, C)) return fail(PTT_EWORKSPACE, "ptt_layernorm_bwd_f32: workspace too small");
+    hipStream_t s = as_stream(stream);
+    const int nch = (rows + LNB_ROWS - 1) / LNB_ROWS;
+    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nch), dim3(256), 0, s, dy, ldg, x, ldx, mean, rstd, weight, rows, C, dx, ldd,
+                       static_cast<double*>(ws));
+    hipLaunchKernelGGL((col_stats_finish2_kernel<1>), dim3(C), dim3(256), 0, s, static_cast<const double*>(ws), nch, C, rows, 0.f, dbias,
+                       dweight, nullptr, BnTail{});
+    return check_launch("layernorm_bwd_kernel");
 }

@@ -13,13 +13,18 @@ and per layer: the q|k|v projection with fc1 folded in, the attention (many poin
 fc_gamma GEMMs read only their head's hd input channels; one frame: the row-job chain of TransformerBlock with fc_gamma
 expanded to its block-diagonal D x D form), proj, a LayerNorm, fc2 and a LayerNorm with the residual. Return contract as
 TransformerBlock: `forward(xyz, features, knn=None, want_attn=True) -> (res, attn)`, attn the LAST layer's
-(B*heads, N, k, hd) tensor, or None when the caller opts out with want_attn=False."""
+(B*heads, N, k, hd) tensor, or None when the caller opts out with want_attn=False.
+
+Training mode on a HIP device (train_ops.mul_block_usable: float32, d_model 512, k 16, heads 1 / 2 / 4 / 8, no dropout) runs on the
+row kernels of ptt_amd/train_ops.py as TransformerBlock's training step does: one kNN and one CSR order of its indices per block,
+per layer the Linears on the row GEMMs, the attention core with the heads' shared fc_gamma, and both LayerNorms on the training
+LayerNorm kernels. Everything else (CPU, other shapes, a non-zero dropout) follows the reference's ops in stock torch."""
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ... import ops
+from ... import ops, train_ops
 from ..model_utils import get_clones, index_points, square_distance
 from .variants import PER_LAYER_MAX_POINTS, SPATIAL_ORDER_MIN_POINTS, _rows2d
 
@@ -113,6 +118,21 @@ class MulHeadTransformerLayer(nn.Module):
         ops.layernorm(o, P['n2w'], P['n2b'], self.norm2.eps, residual=features, out=o)
         return o, attn
 
+    def _train_rows(self, features, knn_idx, rel, order, start, want_attn):
+        """One layer's training step on the row kernels (train_ops); the caller has checked train_ops.mul_block_usable and formed
+        the kNN, the relative coordinates and the CSR order of the neighbour indices (shared by every layer of the block)."""
+        H = self.heads
+        x = train_ops.rows_linear(self.fc1, features)
+        q, kf, vf = (train_ops.rows_linear(m, x) for m in (self.w_qs, self.w_ks, self.w_vs))
+        pos_enc = train_ops.rows_mlp2(self.fc_delta, rel)                          # (B,N,k,D)
+        res, attn = train_ops.attn_core(self.fc_gamma, q, kf, vf, knn_idx, pos_enc, 1.0 / np.sqrt(self.head_dim), order, start, heads=H)
+        res = train_ops.rows_layernorm(self.norm1, train_ops.rows_linear(self.proj, res))
+        res = train_ops.rows_layernorm(self.norm2, train_ops.rows_linear(self.fc2, res), residual=features)
+        if not want_attn:
+            return res, None
+        B, N, k, D = attn.shape                                                    # head-major channels -> (B*heads, N, k, hd)
+        return res, attn.view(B, N, k, H, D // H).permute(0, 3, 1, 2, 4).flatten(0, 1)
+
     def forward(self, xyz, features):
         """The reference's op sequence in stock torch (multitransformer.py:37-63): CPU, training and the calls outside the
         fused envelope. `_rows2d` and the neighbour-axis sum instead of einsum, as TransformerBlock does."""
@@ -180,6 +200,17 @@ class MulTransformerBlock(nn.Module):
             output, attn = features.contiguous(), None
             for i, layer in enumerate(self.layers):
                 output, attn = layer._fused(xyz, output, knn_idx, rel, want_attn and i == len(self.layers) - 1, order)
+            return output, attn
+        if train_ops.mul_block_usable(self, xyz, features):
+            # training mode on a HIP device: the row kernels of ptt_amd/train_ops.py, as TransformerBlock's training branch. kNN: the
+            # HIP kernel (ascending (distance, index), a stable refinement of the reference's argsort), once for all layers
+            knn_idx, rel = ops.knn(xyz.contiguous(), self.k, want_rel=True)
+            if xyz.requires_grad:                                                     # the box head's proposals carry grad
+                rel = train_ops._KnnRel.apply(xyz, knn_idx, rel)
+            order, start = ops.scatter_csr(knn_idx.view(knn_idx.shape[0], -1), knn_idx.shape[1])
+            output, attn = features, None
+            for i, layer in enumerate(self.layers):
+                output, attn = layer._train_rows(output, knn_idx, rel, order, start, want_attn and i == len(self.layers) - 1)
             return output, attn
         output = features
         for layer in self.layers:

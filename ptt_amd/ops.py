@@ -1418,7 +1418,8 @@ class GradFinishPlan(object):
 
     @staticmethod
     def _outputs_per_group(total_chunks):
-        # a function of the chunk count only: the summation tree of a destination is fixed by its job list
+        # a function of the chunk count only: the summation tree of a destination is fixed by its job list. launch_wgrad_finish
+        # (csrc/train_ops.hip) uses the same rule: one job finished here or there is the same sum, bit for bit
         return 4 if total_chunks > 1024 else 8 if total_chunks > 256 else 16 if total_chunks > 64 else 32 if total_chunks > 8 else 64 if total_chunks > 2 else 256
 
     def _build(self, sig):
@@ -1683,6 +1684,74 @@ def rows_gemm_rsum16(x, wpacked, N, residual):
                                                        _ptr(out), int(N), _ptr(plain), int(N), _ptr(gsum), int(N), _stream()),
                    "ptt_rows_gemm_rsum16_f32")
     return plain, out, gsum
+
+
+def rows_gemm_rsum16_heads_supported(x, D, hd):
+    return bool(x.dim() == 2 and x.stride(1) == 1 and x.data_ptr() % 16 == 0 and x.shape[1] == int(D)
+                and _lib.lib().ptt_rows_gemm_rsum16_heads_supported(x.shape[0], int(D), int(hd), x.stride(0)))
+
+
+def rows_gemm_rsum16_heads(x, wpacked, hd, residual):
+    """rows_gemm_rsum16 for a block with D / hd heads (head-major channels) and ONE packed hd x hd weight they share:
+    plain[:, h hd : (h + 1) hd] = x[:, h hd : (h + 1) hd] @ W^T; -> (plain, plain + residual, gsum) — ptt_rows_gemm_rsum16_heads_f32."""
+    _rows(x, "x"); _rows(residual, "residual")
+    rows, D = x.shape
+    hd = int(hd)
+    if tuple(residual.shape) != (rows, D):
+        raise ValueError("rows_gemm_rsum16_heads: residual (rows, D) expected")
+    if hd <= 0 or D % hd or wpacked.numel() < hd * hd:
+        raise ValueError("rows_gemm_rsum16_heads: D %% hd == 0 and a packed hd x hd weight expected (D=%d hd=%d)" % (D, hd))
+    out, plain = (torch.empty((rows, D), dtype=torch.float32, device=x.device) for _ in range(2))
+    gsum = torch.empty((rows // 16, D), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
+        _lib.check(_lib.lib().ptt_rows_gemm_rsum16_heads_f32(_ptr(x), rows, D, hd, x.stride(0), _ptr(wpacked), _ptr(residual),
+                                                             residual.stride(0), _ptr(out), D, _ptr(plain), D, _ptr(gsum), D, _stream()),
+                   "ptt_rows_gemm_rsum16_heads_f32")
+    return plain, out, gsum
+
+
+def layernorm_train_fwd(x, weight, bias, eps, residual=None):
+    """nn.LayerNorm over the rows of x (rows, C) in training mode (+ residual, added after the affine) -> (y, mean (rows,),
+    rstd (rows,)) — ptt_layernorm_train_fwd_f32."""
+    _rows(x, "x")
+    rows, C = x.shape
+    for t, name in ((weight, "weight"), (bias, "bias")):
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise RuntimeError("%s must be a contiguous float32 (%d,) device tensor" % (name, C))
+    if residual is not None:
+        _rows(residual, "residual")
+        if tuple(residual.shape) != (rows, C):
+            raise ValueError("layernorm_train_fwd: residual (rows, C) expected")
+    y = torch.empty((rows, C), dtype=torch.float32, device=x.device)
+    mean, rstd = (torch.empty((rows,), dtype=torch.float32, device=x.device) for _ in range(2))
+    with torch.cuda.device(x.device), _timed('ptt_layernorm_train_fwd_f32'):
+        _lib.check(_lib.lib().ptt_layernorm_train_fwd_f32(_ptr(x), rows, C, x.stride(0) if rows > 1 else C, _ptr(weight), _ptr(bias),
+                                                          float(eps), _ptr(residual),
+                                                          (residual.stride(0) if (residual is not None and rows > 1) else C),
+                                                          _ptr(y), C, _ptr(mean), _ptr(rstd), _stream()), "ptt_layernorm_train_fwd_f32")
+    return y, mean, rstd
+
+
+def layernorm_bwd(dy, x, mean, rstd, weight):
+    """Backward of layernorm_train_fwd: -> (dx (rows, C), dweight (C,), dbias (C,)); the column sums in a fixed order (row chunks,
+    float64 partial slabs, one finish) — ptt_layernorm_bwd_f32. The residual's gradient is dy itself."""
+    _rows(dy, "dy"); _rows(x, "x")
+    rows, C = x.shape
+    if tuple(dy.shape) != (rows, C):
+        raise ValueError("layernorm_bwd: dy (rows, C) expected")
+    for t, name, n in ((mean, "mean", rows), (rstd, "rstd", rows), (weight, "weight", C)):
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise RuntimeError("%s must be a contiguous float32 (%d,) device tensor" % (name, n))
+    dx = torch.empty((rows, C), dtype=torch.float32, device=x.device)
+    dw, db = (torch.empty((C,), dtype=torch.float32, device=x.device) for _ in range(2))
+    if rows == 0:
+        return dx, dw.zero_(), db.zero_()
+    ws = _ws(_lib.lib().ptt_layernorm_bwd_workspace(rows, C), x.device)
+    with torch.cuda.device(x.device), _timed('ptt_layernorm_bwd_f32'):
+        _lib.check(_lib.lib().ptt_layernorm_bwd_f32(_ptr(dy), dy.stride(0) if rows > 1 else C, _ptr(x), x.stride(0) if rows > 1 else C,
+                                                    _ptr(mean), _ptr(rstd), _ptr(weight), rows, C, _ptr(dx), C, _ptr(dw), _ptr(db),
+                                                    _ptr(ws), ws.numel() * 8, _stream()), "ptt_layernorm_bwd_f32")
+    return dx, dw, db
 
 
 # --------------------------------------------------------------------------- Point-Transformer block, training mode

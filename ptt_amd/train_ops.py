@@ -869,19 +869,28 @@ class _AttnCore(torch.autograd.Function):
       * dq = sum_j dt_ij, a reduction pass — the sums over a point's 16 rows come out of the same epilogue;
       * dkf = -scatter_knn(dt): the negation is the scatter's own (ptt_scatter_rows_csr_sub_f32).
     The values are those of the three-function form (dt itself is still written: forming dq / dkf from dt + dvp instead would lose
-    them to cancellation, dvp being ~1000 x larger). Per block and step 11 -> 8 launches, the two largest ATen launches gone."""
+    them to cancellation, dvp being ~1000 x larger). Per block and step 11 -> 8 launches, the two largest ATen launches gone.
+
+    heads > 1 (MulHeadTransformerLayer, multitransformer.py:44-56): the softmax is per channel, so heads only change fc_gamma — ONE
+    hd x hd MLP (hd = D / heads) every head shares — and the caller's scale 1 / sqrt(hd). The reference's head split is head-major in
+    the channel axis (x.view(B, N, H, -1): channel c = h hd + d), so t.view(-1, hd) is a free view with rows * heads rows: fc_gamma
+    forward, its masked input gradient, its weight gradients (summed over heads by the row sum itself) and bias gradients are the
+    row launches above at K = N = hd. Only dt needs a form of its own: in that view a point's 16 neighbour rows lie `heads` apart, so
+    the group-sum GEMM keeps the (rows, D) layout and runs each head's column tile against the shared weight
+    (ptt_rows_gemm_rsum16_heads_f32, hd % 128 == 0: heads 2 and 4 at D = 512; heads 8 takes the three-pass form). heads == 1 is the
+    code path it always was."""
 
     @staticmethod
-    def forward(ctx, q, kf, vf, knn, pos, W1, b1, W2, b2, scale, order, start):
+    def forward(ctx, q, kf, vf, knn, pos, W1, b1, W2, b2, scale, order, start, heads=1):
         ctx.set_materialize_grads(False)
         q, kf, vf, pos = q.contiguous(), kf.contiguous(), vf.contiguous(), pos.contiguous()
         t = ops.pt_pair_input(q, kf, knn, pos)
-        x2 = t.view(-1, t.shape[-1])
+        x2 = t.view(-1, t.shape[-1] // heads)
         h = lin_rows(x2, W1, b1.detach(), relu=True)
-        a = lin_rows(h, W2, b2.detach()).view(*t.shape[:-1], W2.shape[0])
+        a = lin_rows(h, W2, b2.detach()).view(*t.shape[:-1], W2.shape[0] * heads)
         attn, res = ops.pt_attn_train_fwd(a, vf, knn, pos, scale)
         ctx.save_for_backward(x2, h, attn, vf, knn, pos, order, start, W1, W2)      # the weights too: see _RowsLinear
-        ctx.Ws, ctx.bs, ctx.scale = (W1, W2), (b1, b2), float(scale)
+        ctx.Ws, ctx.bs, ctx.scale, ctx.heads = (W1, W2), (b1, b2), float(scale), int(heads)
         ctx.mark_non_differentiable(attn)
         return res, attn
 
@@ -894,7 +903,8 @@ class _AttnCore(torch.autograd.Function):
         dres = dres.contiguous()
         da, dvp = ops.pt_attn_train_bwd(attn, vf, knn, pos, dres, ctx.scale)
         dvf = ops.scatter_rows_det(dvp.view(B, N * k, D), knn.view(B, N * k), N, csr)
-        dy2 = da.view(-1, D)
+        heads = ctx.heads
+        dy2 = da.view(-1, D // heads)
         rows, D1 = h.shape
         dW2 = weight_grad(W2, dy2, h)
         db2 = bias_grad(ctx.bs[1], dy2)
@@ -905,8 +915,12 @@ class _AttnCore(torch.autograd.Function):
             db1 = dz1.sum(0)
         dW1 = weight_grad(W1, dz1, x2)
         Din = W1.shape[1]
-        if ops.rows_gemm_rsum16_supported(dz1, D1, Din) and k == 16 and Din == D:
+        if heads == 1 and ops.rows_gemm_rsum16_supported(dz1, D1, Din) and k == 16 and Din == D:
             dt, dpos, dq = ops.rows_gemm_rsum16(dz1, packed(W1, True), Din, dvp.view(-1, D))
+            dkf = ops.scatter_rows_det(dt.view(B, N * k, D), knn.view(B, N * k), N, csr, negate=True)
+            dq, dpos = dq.view(B, N, D), dpos.view(B, N, k, D)
+        elif heads > 1 and k == 16 and Din * heads == D and ops.rows_gemm_rsum16_heads_supported(dz1.view(-1, D), D, Din):
+            dt, dpos, dq = ops.rows_gemm_rsum16_heads(dz1.view(-1, D), packed(W1, True), Din, dvp.view(-1, D))
             dkf = ops.scatter_rows_det(dt.view(B, N * k, D), knn.view(B, N * k), N, csr, negate=True)
             dq, dpos = dq.view(B, N, D), dpos.view(B, N, k, D)
         else:
@@ -914,17 +928,59 @@ class _AttnCore(torch.autograd.Function):
             dq = dt.sum(dim=2)
             dkf = ops.scatter_rows_det(dt.view(B, N * k, D), knn.view(B, N * k), N, csr).neg_()
             dpos = dt + dvp
-        return dq, dkf, dvf, None, dpos, dW1, small_grad(ctx.bs[0], db1), dW2, db2, None, None, None
+        return dq, dkf, dvf, None, dpos, dW1, small_grad(ctx.bs[0], db1), dW2, db2, None, None, None, None
 
 
-def attn_core(fc_gamma, q, kf, vf, knn, pos, scale, order, start):
-    """-> (res (B,N,D), attn (B,N,k,D)) for fc_gamma = nn.Sequential(Linear, ReLU, Linear) through _AttnCore."""
-    return _AttnCore.apply(q, kf, vf, knn, pos, fc_gamma[0].weight, fc_gamma[0].bias, fc_gamma[2].weight, fc_gamma[2].bias, scale, order, start)
+def attn_core(fc_gamma, q, kf, vf, knn, pos, scale, order, start, heads=1):
+    """-> (res (B,N,D), attn (B,N,k,D)) for fc_gamma = nn.Sequential(Linear, ReLU, Linear) through _AttnCore; heads > 1: fc_gamma is
+    the (D / heads) x (D / heads) MLP the heads share, attn head-major in its channel axis."""
+    return _AttnCore.apply(q, kf, vf, knn, pos, fc_gamma[0].weight, fc_gamma[0].bias, fc_gamma[2].weight, fc_gamma[2].bias, scale, order, start,
+                           int(heads))
 
 
 def pt_block_usable(block, xyz, features):
     return (block.training and xyz.is_cuda and features.dtype == torch.float32 and block.k == 16 and block.d_model % 4 == 0
             and xyz.shape[1] * block.k <= 16384)
+
+
+MUL_BLOCK_HEADS = (1, 2, 4, 8)
+
+
+def mul_block_usable(block, xyz, features):
+    """MulTransformerBlock's training step on the row kernels: training mode, HIP device, float32, k 16, d_model 512, 1 / 2 / 4 / 8
+    heads, at most 16384 (point, neighbour) rows per cloud, no dropout after proj (a non-zero proj_drop stays on stock torch)."""
+    return bool(block.training and xyz.is_cuda and features.is_cuda and features.dtype == torch.float32 and xyz.dtype == torch.float32
+                and block.k == 16 and block.d_model == 512 and block.heads in MUL_BLOCK_HEADS and xyz.shape[1] >= block.k
+                and xyz.shape[1] * block.k <= 16384 and all(layer.proj_drop.p == 0 for layer in block.layers))
+
+
+class _RowsLayerNorm(torch.autograd.Function):
+    """y = LayerNorm_C(x) * w + b (+ residual) over (rows, C) (nn.LayerNorm: norm1 / norm2 of MulHeadTransformerLayer,
+    multitransformer.py:59-60) on ptt_layernorm_train_fwd_f32 / ptt_layernorm_bwd_f32: the forward keeps the rows' mean and rstd, the
+    backward forms dx per row and dw / db as fixed-order column sums; the residual's gradient is dy itself."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps, residual):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        r2 = residual.reshape(-1, x.shape[-1]).contiguous() if residual is not None else None
+        wd = w.detach()
+        y, mean, rstd = ops.layernorm_train_fwd(x2, wd, b.detach(), eps, r2)
+        ctx.save_for_backward(x2, mean, rstd, w)
+        ctx.w, ctx.b, ctx.shape = w, b, x.shape
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, mean, rstd, _ = ctx.saved_tensors
+        dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
+        dx, dw, db = ops.layernorm_bwd(dy2, x2, mean, rstd, ctx.w.detach())
+        return (dx.view(ctx.shape) if ctx.needs_input_grad[0] else None, small_grad(ctx.w, dw) if ctx.needs_input_grad[1] else None,
+                small_grad(ctx.b, db) if ctx.needs_input_grad[2] else None, None, (dy if ctx.needs_input_grad[4] else None))
+
+
+def rows_layernorm(norm, x, residual=None):
+    """nn.LayerNorm `norm` applied to x (..., C) (+ residual) through _RowsLayerNorm."""
+    return _RowsLayerNorm.apply(x, norm.weight, norm.bias, float(norm.eps), residual)
 
 
 def lin_rows(x2, W, b=None, relu=False, residual=None, transpose=False):
