@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 25
+#define PTT_ABI_VERSION 26
 
 enum {
     PTT_OK = 0,
@@ -309,12 +309,18 @@ typedef struct ptt_sa_desc {
     const float* l0_xyz_weight;
     int l0_channels;
     int l0_relu;
-    /* Optional (ABI 22): workspace of at least ptt_sa_compact_workspace(B, M) bytes for the level without point features
-     * (C == 0, use_xyz, nsample 32, 3 -> 64 -> 64 -> 128, the SA0 shape). Non-NULL: two extra launches first reduce every
-     * ball to its DISTINCT rows — a ball's padding slots repeat its first hit, and neighbours with bit-identical (x,y,z)
-     * give bit-identical rows — padded to a class size c in {4, 8, 16, 32}, and the MLP runs on 32 / c balls per 32-row
-     * tile. The max over a multiset equals the max over its distinct members: the output is bitwise the dense one.
-     * Ignored by the other shapes; NULL = every one of the nsample rows (the dense path). idx is not modified.
+    /* Optional (ABI 22; the stream shape ABI 26): workspace of at least ptt_sa_compact_workspace(B, M) bytes, 16-byte
+     * aligned (PTT_EWORKSPACE otherwise). Non-NULL: two extra launches first reduce every ball to its DISTINCT rows, padded
+     * to a class size c in {4, 8, 16, 32}, and the MLP runs on tiles of whole balls of one class. The max over a multiset
+     * equals the max over its distinct members: the output is bitwise the dense one. Two shapes honour it:
+     *   - the level without point features (C == 0, use_xyz, nsample 32, 3 -> 64 -> 64 -> 128, the SA0 shape), 32 / c balls
+     *     per 32-row tile. Distinct = first occurrence of an (x,y,z) bit pattern among the ball's slots: a ball's padding
+     *     slots repeat its first hit, and neighbours with bit-identical coordinates give bit-identical rows;
+     *   - the stream shape (l0_point_term with 128 channels, then 128 -> 128 -> 256, nsample 32, no per-layer scale),
+     *     64 / c balls per 64-row tile. Distinct = real hit: slot s is kept iff s == 0 or idx[s] != idx[0]. A row carries
+     *     its neighbour's feature row, so no coordinate is compared; "distinct rows per ball" below is the real-hit count.
+     * Ignored by the other shapes; NULL = every one of the nsample rows (the dense path). idx is not modified. Worth its two
+     * launches only where most slots are padding and the launch is large (ptt_amd gates it on B * M).
      * Layout (int32 words, T = B*M; read by tests, not an interface to build on):
      *   [0, 4)                 balls per class (c = 4, 8, 16, 32), [4, 16) reserved
      *   [16, 16+T)             distinct rows per ball

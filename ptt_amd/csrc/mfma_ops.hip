@@ -545,7 +545,7 @@ struct SaParams {
     const float* wx;
     float radius;
     long long* dbg;   // dev only (PTT_DEBUG_STAMPS)
-    int32_t* cws;     // sa_lds_kernel: the ball table of sa_compact_kernel (ptt_sa_desc.compact_ws), NULL = every grouped row
+    int32_t* cws;     // sa_lds_kernel, sa_stream_compact_kernel: the ball table of sa_compact_kernel (ptt_sa_desc.compact_ws), NULL = every grouped row
     SaLayerDev L[PTT_SA_MAX_LAYERS];
 };
 
@@ -1488,6 +1488,9 @@ __device__ __forceinline__ void sa_wave_layer(const SaParams& p, const SaLayerDe
 // (x, y, z) bit patterns (integer compares: +0 / -0 and NaN payloads stay apart); the kept indices, in slot order, are
 // padded with the first one to a class size c in {4, 8, 16, 32} and appended to that class's list (one global atomic
 // per class and workgroup). List order depends on the atomics; the pooled outputs do not.
+// XYZ = false (the levels WITH point features, sa_stream_compact_kernel): a row carries its neighbour's feature row, so
+// only the padding is redundant — slot s is kept iff s == 0 or idx[s] != idx[0], no coordinate is read and `ndist` is the
+// ball's real-hit count.
 // ------------------------------------------------------------------------------------------
 constexpr int SAC_HDR = 16;                                  // int32 words ahead of the per-ball arrays
 struct SacTable {
@@ -1504,6 +1507,7 @@ __global__ __launch_bounds__(64) void sa_compact_zero_kernel(int32_t* ws) {
     if (threadIdx.x < 4) ws[threadIdx.x] = 0;
 }
 
+template <bool XYZ>
 __global__ __launch_bounds__(256) void sa_compact_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ idx, int N, int M,
                                                          SacTable tab) {
     __shared__ int s_cnt[4], s_base[4], s_cls[32], s_pos[32], s_nd[32];
@@ -1516,11 +1520,13 @@ __global__ __launch_bounds__(256) void sa_compact_kernel(const float* __restrict
     uint32_t x[SAC_PASSES], y[SAC_PASSES], z[SAC_PASSES];
 #pragma unroll
     for (int q = 0; q < SAC_PASSES; ++q) iv[q] = idx[(size_t)min(g0 + q * 8 + w * 2 + half, T - 1) * 32 + s];
+    if constexpr (XYZ) {
 #pragma unroll
-    for (int q = 0; q < SAC_PASSES; ++q) {
-        const int b = min(g0 + q * 8 + w * 2 + half, T - 1) / M;
-        const uint32_t* pt = reinterpret_cast<const uint32_t*>(xyz) + ((size_t)b * N + iv[q]) * 3;
-        x[q] = pt[0]; y[q] = pt[1]; z[q] = pt[2];
+        for (int q = 0; q < SAC_PASSES; ++q) {
+            const int b = min(g0 + q * 8 + w * 2 + half, T - 1) / M;
+            const uint32_t* pt = reinterpret_cast<const uint32_t*>(xyz) + ((size_t)b * N + iv[q]) * 3;
+            x[q] = pt[0]; y[q] = pt[1]; z[q] = pt[2];
+        }
     }
 #pragma unroll
     for (int q = 0; q < SAC_PASSES; ++q) {
@@ -1528,17 +1534,19 @@ __global__ __launch_bounds__(256) void sa_compact_kernel(const float* __restrict
         const int i0a = __builtin_amdgcn_readlane(iv[q], 0), i0b = __builtin_amdgcn_readlane(iv[q], 32);
         const int i0 = half ? i0b : i0a;
         const bool real = s == 0 || iv[q] != i0;               // a padding slot repeats slot 0
-        const unsigned long long rm = __ballot(real);
-        // the highest real slot of either ball bounds the candidates an earlier slot can duplicate
-        const int J = 31 - __builtin_clz((uint32_t)rm | (uint32_t)(rm >> 32));
-        // both halves' slot j read unconditionally, then selected, and the tests combined bitwise: a readlane under a
-        // per-lane condition or a short-circuit && turns the loop into divergent branches (measured 20-26 us a launch)
         int dup = 0;
-        for (int j = 0; j < J; ++j) {
-            const uint32_t xa = __builtin_amdgcn_readlane(x[q], j), xb = __builtin_amdgcn_readlane(x[q], 32 + j);
-            const uint32_t ya = __builtin_amdgcn_readlane(y[q], j), yb = __builtin_amdgcn_readlane(y[q], 32 + j);
-            const uint32_t za = __builtin_amdgcn_readlane(z[q], j), zb = __builtin_amdgcn_readlane(z[q], 32 + j);
-            dup |= (int)(j < s) & (int)(x[q] == (half ? xb : xa)) & (int)(y[q] == (half ? yb : ya)) & (int)(z[q] == (half ? zb : za));
+        if constexpr (XYZ) {
+            const unsigned long long rm = __ballot(real);
+            // the highest real slot of either ball bounds the candidates an earlier slot can duplicate
+            const int J = 31 - __builtin_clz((uint32_t)rm | (uint32_t)(rm >> 32));
+            // both halves' slot j read unconditionally, then selected, and the tests combined bitwise: a readlane under a
+            // per-lane condition or a short-circuit && turns the loop into divergent branches (measured 20-26 us a launch)
+            for (int j = 0; j < J; ++j) {
+                const uint32_t xa = __builtin_amdgcn_readlane(x[q], j), xb = __builtin_amdgcn_readlane(x[q], 32 + j);
+                const uint32_t ya = __builtin_amdgcn_readlane(y[q], j), yb = __builtin_amdgcn_readlane(y[q], 32 + j);
+                const uint32_t za = __builtin_amdgcn_readlane(z[q], j), zb = __builtin_amdgcn_readlane(z[q], 32 + j);
+                dup |= (int)(j < s) & (int)(x[q] == (half ? xb : xa)) & (int)(y[q] == (half ? yb : ya)) & (int)(z[q] == (half ? zb : za));
+            }
         }
         const bool keep = real && !dup;
         const unsigned long long km = __ballot(keep);
@@ -1594,16 +1602,28 @@ __global__ __launch_bounds__(256) void sa_compact_kernel(const float* __restrict
 #define PTT_SAL_WAVES 12     // waves per workgroup (three per SIMD: 148 VGPRs)
 #endif
 
-// the tile `j` of the compact table: class k, first list position, balls in it
-struct SacTile {
+// the tile `j` of the compact table: class k, first list position, balls in it. ROWS = rows of a tile (32: one
+// accumulator tile per wave, sa_lds_kernel; 64: the two row tiles of sa_stream_compact_kernel): ROWS / 4 >> k balls
+template <int ROWS>
+struct SacTileT {
+    static constexpr int LG = ROWS == 32 ? 3 : 4;            // log2 of the balls of a class-4 tile
+    static_assert(ROWS == 32 || ROWS == 64, "32- or 64-row tiles");
     int k, first, n;
+    // running tile counts of the four classes out of the table's (clamped) ball counts
+    __device__ __forceinline__ static void count(const int32_t* ws, int total, int (&cnt)[4], int (&tiles)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cnt[k] = min(max(ws[k], 0), total);
+            tiles[k] = (k ? tiles[k - 1] : 0) + ((cnt[k] + ((1 << LG) >> k) - 1) >> (LG - k));
+        }
+    }
     __device__ __forceinline__ void at(int j, const int (&tiles)[4], const int (&cnt)[4]) {
         k = j < tiles[0] ? 0 : j < tiles[1] ? 1 : j < tiles[2] ? 2 : 3;
         // selects, not indexing: a run-time index would put both arrays in scratch
         const int j0 = k == 0 ? 0 : k == 1 ? tiles[0] : k == 2 ? tiles[1] : tiles[2];
         const int nk = k == 0 ? cnt[0] : k == 1 ? cnt[1] : k == 2 ? cnt[2] : cnt[3];
-        first = (j - j0) << (3 - k);                         // 8 >> k balls per tile
-        n = min(8 >> k, nk - first);
+        first = (j - j0) << (LG - k);                        // ROWS / 4 >> k balls per tile
+        n = min((1 << LG) >> k, nk - first);
     }
     // row `s` of the tile: (neighbour index, ball)
     __device__ __forceinline__ void row(const SacTable& tab, int s, int& n_out, int& ball) const {
@@ -1612,57 +1632,58 @@ struct SacTile {
         ball = tab.list(k)[first + (inb ? cl : 0)];
     }
 };
+using SacTile = SacTileT<32>;
 
-// compact tile epilogue: the max over each ball's c rows (c = 4 << k), layer 2's shift, ReLU — the same arithmetic as
-// sas_pool on fewer rows — stored for the tile's n balls. Rows of ball g: registers 4q..4q+3 of half-wave g & 1
-// (q = g >> 1) for c = 4; registers 4g..4g+3 of both halves for c = 8; 8g..8g+7 of both halves for c = 16.
-// `ball`: the ball of this lane's row (ball g of the tile is the one of row g c, read from that lane).
-__device__ __forceinline__ void sac_store(const SaParams& p, const SacTile& tc, int ball, const f32x16 (&acc)[4], const float* cst,
-                                          int half, int col, int osb, int osm, int osc) {
-    const int k = tc.k, relu = p.L[2].relu;
+// compact tile epilogue: the max over each ball's c rows (c = 4 << k) of NU 32 x 32 accumulator tiles (column tiles of the
+// same 32 rows), layer 2's shift, ReLU — the same arithmetic as sas_pool on fewer rows — stored for the tile's n >= 1
+// balls. Rows of ball g: registers 4q..4q+3 of half-wave g & 1 (q = g >> 1) for c = 4; registers 4g..4g+3 of both halves
+// for c = 8; 8g..8g+7 of both halves for c = 16.
+// `ball`: the ball of this lane's row (lane & 31; ball g of the tile is the one of row g c, read from that lane).
+// sh[u], o[u]: the shift and the output address of this lane's column in column tile u.
+template <int NU>
+__device__ __forceinline__ void sac_store(int k, int n, int ball, int M, const f32x16 (&acc)[NU], const float (&sh)[NU],
+                                          float* const (&o)[NU], int relu, int half, int osb, int osm) {
     int ob[8];                                               // output offset of ball g (wave-uniform)
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
         if (g >= (8 >> k)) break;
-        const int id = __builtin_amdgcn_readlane(ball, g << (2 + k)), b = id / p.M;
-        ob[g] = b * osb + (id - b * p.M) * osm;
+        const int id = __builtin_amdgcn_readlane(ball, g << (2 + k)), b = id / M;
+        ob[g] = b * osb + (id - b * M) * osm;
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const float sh = cst[(6 + u) * 64];
-        float* o = p.out + (u * 32 + col) * osc;
+    for (int u = 0; u < NU; ++u) {
         const f32x16& a = acc[u];
         if (k == 3) {
-            const float mx = sas_pool(a, sh, relu);
-            if (half == 0) o[ob[0]] = mx;
+            const float mx = sas_pool(a, sh[u], relu);
+            if (half == 0) o[u][ob[0]] = mx;
         } else if (k == 2) {
             float m0 = a[0], m1 = a[8];
 #pragma unroll
             for (int r = 1; r < 8; ++r) { m0 = fmaxf(m0, a[r]); m1 = fmaxf(m1, a[8 + r]); }
-            m0 = max_halves(m0) + sh; m1 = max_halves(m1) + sh;
+            m0 = max_halves(m0) + sh[u]; m1 = max_halves(m1) + sh[u];
             if (relu) { m0 = fmaxf(m0, 0.f); m1 = fmaxf(m1, 0.f); }
-            if (half < tc.n) o[half ? ob[1] : ob[0]] = half ? m1 : m0;       // half-wave h stores ball h
+            if (half < n) o[u][half ? ob[1] : ob[0]] = half ? m1 : m0;       // half-wave h stores ball h
         } else {
             float m[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) m[q] = fmaxf(fmaxf(a[4 * q], a[4 * q + 1]), fmaxf(a[4 * q + 2], a[4 * q + 3]));
             if (k == 1) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) m[q] = max_halves(m[q]) + sh;
+                for (int q = 0; q < 4; ++q) m[q] = max_halves(m[q]) + sh[u];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {                // half-wave h stores balls 2h, 2h + 1
                     const int g = 2 * half + i;
                     float v = half ? m[2 + i] : m[i];
                     if (relu) v = fmaxf(v, 0.f);
-                    if (g < tc.n) o[half ? ob[2 + i] : ob[i]] = v;
+                    if (g < n) o[u][half ? ob[2 + i] : ob[i]] = v;
                 }
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int g = 2 * q + half;
-                    float v = m[q] + sh;
+                    float v = m[q] + sh[u];
                     if (relu) v = fmaxf(v, 0.f);
-                    if (g < tc.n) o[half ? ob[2 * q + 1] : ob[2 * q]] = v;
+                    if (g < n) o[u][half ? ob[2 * q + 1] : ob[2 * q]] = v;
                 }
             }
         }
@@ -1682,11 +1703,7 @@ void sa_lds_kernel(SaParams p) {
     SacTable tab{p.cws, total};
     int cnt[4], tiles[4];                                    // compact: balls per class, running tile counts
     if constexpr (COMPACT) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            cnt[k] = min(max(p.cws[k], 0), total);
-            tiles[k] = (k ? tiles[k - 1] : 0) + ((cnt[k] + (8 >> k) - 1) >> (3 - k));
-        }
+        SacTile::count(p.cws, total, cnt, tiles);
         if (logical_block() >= tiles[3]) return;             // no tile for this workgroup: skip the weight load
     }
     {
@@ -1843,7 +1860,9 @@ void sa_lds_kernel(SaParams p) {
                 for (int u = 0; u < 4; ++u) wb[u] = wm[u];
             }
             if constexpr (COMPACT) {
-                sac_store(p, tc, g_cur, acc, cst, half, col, osb, osm, osc);
+                const float sh2[4] = {cst[6 * 64], cst[7 * 64], cst[8 * 64], cst[9 * 64]};
+                float* const o[4] = {p.out + col * osc, p.out + (32 + col) * osc, p.out + (64 + col) * osc, p.out + (96 + col) * osc};
+                sac_store<4>(tc.k, tc.n, g_cur, M, acc, sh2, o, p.L[2].relu, half, osb, osm);
             } else {
                 float* o = p.out + (ce.b * osb + ce.m * osm);
 #pragma unroll
@@ -1854,6 +1873,117 @@ void sa_lds_kernel(SaParams p) {
             }
         }
         if constexpr (COMPACT) { tc = tx; g_cur = g_next; } else ce = nx;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The stream shape (SA1 / SA2: hoisted 128-channel layer 0, 128 -> 128 -> 256, 32 neighbours) on the balls' REAL hits only
+// (ptt_sa_desc.compact_ws): ball query pads a ball's 32 slots with its first hit, a padded row is bit-identical to slot 0
+// and the rows are max-pooled, so the table of sa_compact_kernel<false> keeps every bit. A 64-row tile holds 64 / c balls
+// of one class c; every row takes its OWN centre from the table (the dense kernel: the tile's two centres), and the pool
+// runs per ball over accumulator rows [g c, (g + 1) c) of a 32-row half (sac_store). Per row the arithmetic is
+// sa_stream_kernel's: the h0 FMA chain (sas_pair_store), layer 1 with its shift as the C operand, the same fp32 MFMA in
+// the same K order, layer 2's shift after the pool. What is left of the work (an eighth to a quarter of the dense tiles
+// on sparse balls) does not pay for the dense kernel's software pipeline: the phases of a tile run one after the other
+// between barriers, and the second workgroup of the CU fills the gaps. The tile count is known on the device only:
+// a fixed grid walks it (tile j -> workgroup j % G).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 2) void sa_stream_compact_kernel(SaParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const P = smem;                                 // h0 of the tile
+    float* const Q = smem + SAS_TILE;                      // h1 of the tile
+    float* const meta = smem + 2 * SAS_TILE;               // [64 rows][off, dx, dy, dz]
+    int* const sball = reinterpret_cast<int*>(meta + 64 * 4);   // [64 rows] the row's ball
+    const int t = threadIdx.x, lane = t & 63, half = lane >> 5, sub = half, q = lane & 31, col = q;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int total = p.B * p.M, M = p.M, N = p.N;
+    const SacTable tab{p.cws, total};
+    int cnt[4], tiles[4];
+    SacTileT<64>::count(p.cws, total, cnt, tiles);
+    if ((int)blockIdx.x >= tiles[3]) return;
+    const SaLayerDev& L1 = p.L[0];
+    const SaLayerDev& L2 = p.L[1];
+    const __amdgpu_buffer_rsrc_t rf = weight_rsrc(p.feat);
+    const __amdgpu_buffer_rsrc_t wr1 = weight_rsrc(L1.Wp), wr2 = weight_rsrc(L2.Wp);
+    const int wvoff = (w * 64 + lane) * 16;
+    constexpr int WK1 = 4 * 1024, WK2 = 8 * 1024;          // bytes per K-block of the packed weights (NT = 4 / 8)
+    const f32x4 wx0 = *reinterpret_cast<const f32x4*>(p.wx + q * 4);
+    const f32x4 wx1 = *reinterpret_cast<const f32x4*>(p.wx + 128 + q * 4);
+    const f32x4 wx2 = *reinterpret_cast<const f32x4*>(p.wx + 256 + q * 4);
+    const float sh1 = L1.shift ? L1.shift[w * 32 + col] : 0.f;
+    const float sh2[2] = {L2.shift ? L2.shift[w * 32 + col] : 0.f, L2.shift ? L2.shift[(w + 4) * 32 + col] : 0.f};
+    f32x16 sh1v;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sh1v[r] = sh1;
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float floor0 = p.l0_relu ? 0.f : -__builtin_inff();
+    const float rdiv = p.normalize ? p.radius : 1.0f;
+    const int osb = (int)p.osb, osm = (int)p.osm;
+    float* const o[2] = {p.out + (w * 32 + col) * (int)p.osc, p.out + ((w + 4) * 32 + col) * (int)p.osc};
+
+    for (int j = blockIdx.x; j < tiles[3]; j += (int)gridDim.x) {
+        SacTileT<64> tc;
+        tc.at(j, tiles, cnt);
+        // ---- row meta: (byte offset of the neighbour's per-point term row, relative coordinates), the row's ball ----
+        if (t < 64) {
+            int n, ball;
+            tc.row(tab, t, n, ball);
+            const int flat = (ball / M) * N + n;
+            const float x = p.xyz[(size_t)flat * 3 + 0], y = p.xyz[(size_t)flat * 3 + 1], z = p.xyz[(size_t)flat * 3 + 2];
+            const float cx = p.new_xyz[(size_t)ball * 3 + 0], cy = p.new_xyz[(size_t)ball * 3 + 1], cz = p.new_xyz[(size_t)ball * 3 + 2];
+            const float dx = (x - cx) / rdiv, dy = (y - cy) / rdiv, dz = (z - cz) / rdiv;
+            const int off = flat * (128 * (int)sizeof(float));
+            *reinterpret_cast<f32x4*>(meta + t * 4) = f32x4{__builtin_bit_cast(float, off), dx, dy, dz};
+            sball[t] = ball;
+        }
+        __syncthreads();
+        // ---- h0 = relu(term + Wx . rel) of this wave's 16 rows -> P ----
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            f32x4 m;
+            const f32x4 v = sas_pair_load(meta, rf, w, i, sub, q, m);
+            sas_pair_store(P, w, i, sub, q, v, m, wx0, wx1, wx2, floor0);
+        }
+        const int ballr[2] = {sball[col], sball[32 + col]};
+        __syncthreads();
+        // ---- layer 1: 128 -> 128, column tile w of both row tiles -> Q ----
+        {
+            f32x16 acc1[2] = {sh1v, sh1v};
+            const float* arow = P + (lane & 31) * SAS_LDK + 4 * half;
+#pragma unroll
+            for (int kb = 0; kb < 16; ++kb) {
+                const f32x4 b = weight_load(wr1, wvoff, kb * WK1);
+                const f32x4 a[2] = {*reinterpret_cast<const f32x4*>(arow + kb * 8),
+                                    *reinterpret_cast<const f32x4*>(arow + 32 * SAS_LDK + kb * 8)};
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int rt = 0; rt < 2; ++rt) acc1[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[rt][jj], b[jj], acc1[rt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Q[(rt * 32 + tile_row(r, half)) * SAS_LDK + w * 32 + col] = fmaxf(acc1[rt][r], 0.f);
+        }
+        __syncthreads();
+        // ---- layer 2: 128 -> 256, column tiles w, w + 4; the max over each ball's rows, shift, ReLU ----
+        {
+            f32x16 acc[2][2] = {{zero16, zero16}, {zero16, zero16}};
+            const float* arow = Q + (lane & 31) * SAS_LDK + 4 * half;
+#pragma unroll
+            for (int kb = 0; kb < 16; ++kb) {
+                const f32x4 b[2] = {weight_load(wr2, wvoff, kb * WK2), weight_load(wr2, wvoff, kb * WK2 + 4 * 1024)};
+                const f32x4 a[2] = {*reinterpret_cast<const f32x4*>(arow + kb * 8),
+                                    *reinterpret_cast<const f32x4*>(arow + 32 * SAS_LDK + kb * 8)};
+                gemm_mfma_block<2, 2, 2>(a, b, acc);
+            }
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                const int n = tc.n - rt * (8 >> tc.k);       // balls of this 32-row half that exist
+                if (n <= 0) continue;
+                sac_store<2>(tc.k, n, ballr[rt], M, acc[rt], sh2, o, L2.relu, half, osb, osm);
+            }
+        }
     }
 }
 
@@ -2319,7 +2449,7 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
             p.cws = static_cast<int32_t*>(d->compact_ws);
             hipLaunchKernelGGL(sa_compact_zero_kernel, dim3(1), dim3(64), 0, s, p.cws);
             if ((rc = check_launch("sa_compact_zero_kernel"))) return rc;
-            hipLaunchKernelGGL(sa_compact_kernel, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
+            hipLaunchKernelGGL(sa_compact_kernel<true>, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
                                SacTable{p.cws, total_centres});
             if ((rc = check_launch("sa_compact_kernel"))) return rc;
             if (wgs > 256 * PTT_SAL_WGS) wgs = 256 * PTT_SAL_WGS;
@@ -2364,6 +2494,23 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
         p.chunk = (p.tiles + wgs - 1) / wgs;
         if (dev_switches().sa_chunk > 0 && p.chunk > dev_switches().sa_chunk) p.chunk = dev_switches().sa_chunk;
         wgs = (p.tiles + p.chunk - 1) / p.chunk;
+        if (d->compact_ws) {
+            // the balls' real hits first (sa_compact_kernel<false>), then 64-row tiles of 2 - 16 balls. As at SA0 the tile
+            // count is known on the device only: a fixed grid of at most two workgroups per CU walks it
+            if (d->compact_ws_bytes < ptt_sa_compact_workspace(d->B, d->M) || (reinterpret_cast<uintptr_t>(d->compact_ws) & 15))
+                return fail(PTT_EWORKSPACE, "ptt_sa_fused_fwd_f32: compact_ws needs %zu bytes, 16-byte aligned (got %zu)",
+                            ptt_sa_compact_workspace(d->B, d->M), d->compact_ws_bytes);
+            p.cws = static_cast<int32_t*>(d->compact_ws);
+            hipLaunchKernelGGL(sa_compact_zero_kernel, dim3(1), dim3(64), 0, s, p.cws);
+            if ((rc = check_launch("sa_compact_zero_kernel"))) return rc;
+            hipLaunchKernelGGL(sa_compact_kernel<false>, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
+                               SacTable{p.cws, total_centres});
+            if ((rc = check_launch("sa_compact_kernel"))) return rc;
+            const int lds = (2 * SAS_TILE + 64 * 4 + 64) * (int)sizeof(float);
+            if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_stream_compact_kernel), lds))) return rc;
+            hipLaunchKernelGGL(sa_stream_compact_kernel, dim3(p.tiles < 512 ? p.tiles : 512), dim3(256), lds, s, p);
+            return check_launch("sa_stream_compact_kernel");
+        }
         const int lds = (2 * SAS_TILE + 4 * 16 * 4) * (int)sizeof(float);
         if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_stream_kernel<32>), lds))) return rc;
         hipLaunchKernelGGL((sa_stream_kernel<32>), dim3(wgs), dim3(256), lds, s, p);

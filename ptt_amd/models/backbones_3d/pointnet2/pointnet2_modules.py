@@ -24,6 +24,24 @@ from .... import ops, train_ops
 from . import pointnet2_utils
 from . import pytorch_utils as pt_utils
 
+# Fewest balls (B * M) of a launch that `compact=True` sends to the compact stream kernel. The compact call is three
+# launches and never takes less than 23 us; the dense kernel takes 16-18 us up to 512 balls. Measured at the search
+# branch's last level (N = 256, M = 128; graph-replayed, us per call, dense / compact;
+# profiles/sa2c_stream_dense_vs_compact.log):
+#   balls            128 (one frame)   512           1024 (8 frames)   2048          6144 (48 frames)
+#   car (1.4 hits)   16.2 / 23.1       17.5 / 23.1   31.0 / 23.4       56.0 / 23.7   155.1 / 37.7
+#   ped (25 hits)    15.9 / 22.5       17.7 / 23.8   30.4 / 34.2       52.9 / 58.2   148.1 / 133.8
+# Below 1024 balls dense always wins (one tracklet frame is a chain of dependent launches: +6.5 us and two more launches
+# per level); at 1024 sparse balls gain 8 us and full ones lose 4; from 2048 sparse balls gain 32 us or more against 5 lost
+# on full ones (scripts/sa_stream_compact_bench.py). One tracklet frame never reaches this gate: its path does not pass
+# `compact` at all (docs/experiments.md has its latency against the parent).
+STREAM_COMPACT_MIN_BALLS = 2048
+# ... and the most points per cloud of the level (N), a proxy for ball density: the 16384-point stress clouds have 4096
+# points at the last search level and 22.5 real hits per ball. Measured with this gate lifted: the stress step 23.09 / 23.11
+# -> 23.75 / 23.76 ms (+2.8 %, two lines each, same session; spread 0.03 ms), although the launch alone costs the same
+# (1539 dense / 1532 compact us). Every car / ped / train level has at most 512 points.
+STREAM_COMPACT_MAX_POINTS = 1024
+
 
 class PointnetSAModuleVotes(nn.Module):
     def __init__(self, *, mlp: List[int], radius: float = None, nsample: int = None, bn: bool = True,
@@ -150,10 +168,13 @@ class PointnetSAModuleVotes(nn.Module):
         return layers, hoist
 
     # ------------------------------------------------------------------ forward (reference :57-90)
-    def forward(self, xyz: torch.Tensor, features: torch.Tensor, npoint: int, inds: torch.Tensor = None, pre=None):
+    def forward(self, xyz: torch.Tensor, features: torch.Tensor, npoint: int, inds: torch.Tensor = None, pre=None,
+                compact: bool = False):
         """`pre` (an extension of the reference signature, eval mode on a HIP device only): (new_xyz, idx, inds64) of this level
         already computed by the caller — the backbone forms the ball queries of all three levels of a branch in one launch
-        when it runs one tracklet frame (ops.sa_levels_point_jobs)."""
+        when it runs one tracklet frame (ops.sa_levels_point_jobs).
+        `compact` (same conditions): a level WITH point features pools each ball's real hits only (the stream shape of
+        ops.sa_fused_forward, bitwise the same output) when the launch has at least STREAM_COMPACT_MIN_BALLS balls."""
         fused = self._fusable(xyz, features)
         if pre is not None and not fused:
             pre = None
@@ -215,7 +236,9 @@ class PointnetSAModuleVotes(nn.Module):
                                               act=1 if L2[5] else 0, out=pooled)])
                     return new_xyz, pooled.transpose(1, 2), inds64
                 new_features = ops.sa_fused_forward(xyz, new_xyz, idx, None, [L[:6] for L in layers[1:]], self.radius, True,
-                                                    self.normalize_xyz, point_major_out=True, l0=(term, wx, relu0))
+                                                    self.normalize_xyz, point_major_out=True, l0=(term, wx, relu0),
+                                                    compact=(bool(compact) and B * M >= STREAM_COMPACT_MIN_BALLS
+                                                             and xyz.shape[1] <= STREAM_COMPACT_MAX_POINTS))
             else:
                 # the level without point features (SA0) pools each ball's distinct rows only: same bits, a fraction of
                 # the rows (ball-query padding and the resampled clouds' repeated points)

@@ -76,10 +76,12 @@ class PointNet2BackboneLight(nn.Module):
             ops.publish_params(xyz.device, replaced=False)
         return cache[key]
 
-    def branch_forward(self, pts, npoints: List, inds0=None, want_knn=0):
+    def branch_forward(self, pts, npoints: List, inds0=None, want_knn=0, compact_levels=()):
         """`inds0`: optional precomputed level-0 sample indices (B, npoints[0]) — the SA module accepts
         caller-supplied indices exactly as the reference's does (pointnet2_modules.py:60,76-77); a pipelined
-        driver computes them for batch n+1 while batch n is in the dense kernels."""
+        driver computes them for batch n+1 while batch n is in the dense kernels.
+        `compact_levels`: the levels with point features (1, 2) that pool each ball's real hits only (the `compact`
+        keyword of PointnetSAModuleVotes.forward; same values). The one-frame path below keeps them dense."""
         xyz, features = self._break_up_pc(pts)
         sa = self.model_cfg.SA_CONFIG
         one_frame = (not self.training and xyz.is_cuda and features is None and len(self.SA_modules) == 3
@@ -109,8 +111,8 @@ class PointNet2BackboneLight(nn.Module):
                                                       pre=(levels[2][0], levels[2][1], seq[2]))
         else:
             xyz, features, inds0 = self.SA_modules[0](xyz=xyz, features=features, npoint=npoints[0], inds=inds0)
-            xyz, features, inds1 = self.SA_modules[1](xyz=xyz, features=features, npoint=npoints[1])
-            xyz, features, inds2 = self.SA_modules[2](xyz=xyz, features=features, npoint=npoints[2])
+            xyz, features, inds1 = self.SA_modules[1](xyz=xyz, features=features, npoint=npoints[1], compact=1 in compact_levels)
+            xyz, features, inds2 = self.SA_modules[2](xyz=xyz, features=features, npoint=npoints[2], compact=2 in compact_levels)
         point_features = self._cov_final(features)
         assert inds1.dtype == inds2.dtype == torch.int64, 'index type must be int64, not {}'.format(inds2.dtype)
         if all(m.sample_method in ('rs', 'sequence') for m in self.SA_modules[1:]) and inds0.shape[1] >= npoints[2]:
@@ -138,8 +140,11 @@ class PointNet2BackboneLight(nn.Module):
         kernels fill the CUs the other's FPS leaves idle. `inds` = optional (search, template) level-0 FPS indices."""
         sa = self.model_cfg.SA_CONFIG
         i_s, i_t = inds if inds is not None else (None, None)
+        # eval mode on a HIP device: the search branch's last level alone runs on the balls' real hits — its launch keeps the
+        # fewest tiles per ball; the other three stream launches stay dense (docs/experiments.md "Stream kernel on real hits")
+        last = (len(self.SA_modules) - 1,) if (search_points.is_cuda and not self.training) else ()
         if not (self.overlap_branches and search_points.is_cuda and not self.training):
-            r = self.branch_forward(search_points, sa.NPOINTS_SEARCH, i_s, want_knn=self.seed_knn)
+            r = self.branch_forward(search_points, sa.NPOINTS_SEARCH, i_s, want_knn=self.seed_knn, compact_levels=last)
             t_seeds, t_feats, t_inds = self.branch_forward(template_points, sa.NPOINTS_TEMPLATE, i_t)
         else:
             if self._side_stream is None or self._side_stream.device != search_points.device:
@@ -148,7 +153,7 @@ class PointNet2BackboneLight(nn.Module):
             side = graph_policy.branch(main, self._side_stream)       # inside a capture the policy may keep the branch in line
             with torch.cuda.stream(side):
                 t_seeds, t_feats, t_inds = self.branch_forward(template_points, sa.NPOINTS_TEMPLATE, i_t)
-            r = self.branch_forward(search_points, sa.NPOINTS_SEARCH, i_s, want_knn=self.seed_knn)
+            r = self.branch_forward(search_points, sa.NPOINTS_SEARCH, i_s, want_knn=self.seed_knn, compact_levels=last)
             graph_policy.join(main, side)
             if side is not main:
                 for t in (t_seeds, t_feats, t_inds, template_points):

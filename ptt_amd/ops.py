@@ -425,9 +425,11 @@ def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, 
     layers: list of (wpacked, scale|None, shift|None, cin, cout, relu); layers[0] packed with rot=3 if use_xyz.
     l0: optional (point_term (B,N,C0) contiguous, xyz_weight (3,C0), relu) — layer 0 hoisted to one row per point
     (include/ptt_hip.h, ptt_sa_desc.l0_*); then features must be None and `layers` are the remaining layers.
-    compact: the level without point features (SA0 shape) runs its MLP on every ball's distinct rows only, bitwise the
-    same output (ptt_sa_desc.compact_ws): True allocates the workspace, a device tensor of at least
-    ptt_sa_compact_workspace(B, M) bytes is used as it (afterwards it holds the ball table). Other shapes ignore it.
+    compact: the MLP runs on every ball's distinct rows only, bitwise the same output (ptt_sa_desc.compact_ws): True
+    allocates the workspace, a 16-byte aligned device tensor of at least ptt_sa_compact_workspace(B, M) bytes is used as
+    it (afterwards it holds the ball table). Two shapes honour it: the level without point features (SA0 shape; distinct =
+    first occurrence of a coordinate bit pattern) and the stream shape (l0 with 128 channels, layers 128 -> 128 -> 256,
+    32 neighbours; distinct = real hit, slot s with s == 0 or idx[s] != idx[0]). Other shapes ignore it.
     Returns (B,Cout,M); with point_major_out it is a transposed view of (B,M,Cout) storage."""
     _chk(xyz, "xyz", torch.float32, 3)
     _chk(new_xyz, "new_xyz", torch.float32, 3)
