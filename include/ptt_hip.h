@@ -18,6 +18,14 @@
  *     string.
  *   - clouds are (B, N, 3) fp32 "xyz"; indices are int32 as in the reference
  *     (pointnet2_utils.py:58-85, 265-294).
+ *
+ * This file is also what Python binds from: ptt_amd/_lib.py reads it at import and takes the list of
+ * entry points, every restype / argtypes and the integer PTT_* constants from the text below — there is
+ * no second table to edit. Keep it plain C that a small parser reads: one prototype per `;`, `(void)`
+ * for no parameters, scalar parameters of the types int, int32_t, uint32_t, int64_t, long long, size_t,
+ * float, double and ptt_stream_t, any pointer otherwise (a new scalar type is added to CTYPES in
+ * _lib.py, or the import raises); constants as `#define PTT_NAME <decimal>`. Structures are still mirrored by
+ * hand in _lib.py, and tests compare those mirrors with what the C compiler makes of this file.
  */
 #ifndef PTT_HIP_H
 #define PTT_HIP_H

@@ -1,54 +1,83 @@
 """ctypes binding of libptt_hip.so (the C ABI declared in include/ptt_hip.h).
 
+The header is the declaration: it is read once at import, and the list of entry points, their restype / argtypes and the
+PTT_* constants all come from it. Only the structures are restated here (tests compare them with what gcc makes of the header).
 There is no fallback: if the shared library is missing or fails to load, every op raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_size_t, c_uint32, c_void_p
+import re
+from ctypes import Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_size_t, c_uint32, c_void_p
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libptt_hip.so")
+from .build import HEADER as HEADER_PATH, LIB as LIB_PATH
 
-PTT_SA_MAX_LAYERS = 4
-ABI_VERSION = 26            # PTT_ABI_VERSION of include/ptt_hip.h these structures mirror
 
-# every symbol include/ptt_hip.h declares (tests check the library exports all of them)
-EXPORTS = [
-    "ptt_version", "ptt_error_name", "ptt_last_error_string",
-    "ptt_fps_f32", "ptt_fps_ws_f32", "ptt_spatial_order_f32", "ptt_ball_query_grid_workspace", "ptt_ball_query_grid_f32",
-    "ptt_centres_ball_query_grid_f32", "ptt_gather_f32", "ptt_gather_grad_f32", "ptt_select_centres_f32", "ptt_ball_query_f32",
-    "ptt_group_f32", "ptt_group_grad_f32", "ptt_scatter_add_det_workspace", "ptt_scatter_add_det_f32",
-    "ptt_knn_f32", "ptt_knn_rel_f32",
-    "ptt_packed_weight_elems", "ptt_pack_weight_f32", "ptt_pack_weight_rot_f32", "ptt_linear_f32",
-    "ptt_sa_fused_fwd_f32", "ptt_xcorr_fused_fwd_f32", "ptt_cosine_map_f32", "ptt_pt_attn_pair_f32",
-    "ptt_crop_compact_f32", "ptt_regularize_f32", "ptt_mt19937_fill", "ptt_select_box_f32",
-    "ptt_track_crop_bounds", "ptt_track_box_by_offset",
-    "ptt_bn_stats_workspace", "ptt_bn_stats_f32", "ptt_bn_apply_f32", "ptt_bn_bwd_f32", "ptt_pool_rows_f32",
-    "ptt_pool_rows_bwd_f32", "ptt_linear_wgrad_workspace", "ptt_linear_wgrad_f32",
-    "ptt_pack_weight_strided_f32", "ptt_linear_batched_f32", "ptt_softmax_rows_f32", "ptt_layernorm_f32",
-    "ptt_gather_rows_f32", "ptt_scatter_csr_i32", "ptt_scatter_rows_csr_f32",
-    "ptt_pt_pair_input_f32", "ptt_pt_attn_train_fwd_f32", "ptt_pt_attn_train_bwd_f32", "ptt_linear_act_in_f32",
-    "ptt_centres_ball_query_f32",
-    "ptt_bn_sums_f64", "ptt_bn_finish_f64", "ptt_bn_bwd_sums_f64", "ptt_bn_bwd_apply_f32",
-    "ptt_rows_mlp_f32",
-    "ptt_rows_gemm_supported", "ptt_rows_gemm_stat_chunks", "ptt_rows_gemm_f32", "ptt_rows_gemm_masked_f32", "ptt_bn_finish_partials_f32",
-    "ptt_bn_sums_partials_f64", "ptt_linear_wgrad2_workspace", "ptt_linear_wgrad2_f32",
-    "ptt_bn_bwd_pooled_f32", "ptt_bn_bwd_pooled_sums_f64", "ptt_bn_bwd_pooled_apply_f32",
-    "ptt_pt_pair_input_ld_f32", "ptt_pt_attn_fwd_ld_f32",
-    "ptt_rows_gemm_bnbwd_f32", "ptt_bn_bwd_from_partials_f32", "ptt_bn_bwd_sums_partials_f64",
-    "ptt_bn_bwd_consts_f32", "ptt_bn_bwd_pooled_consts_f32", "ptt_rows_gemm_bnbwd_fused_supported", "ptt_rows_gemm_bnbwd_fused_f32",
-    "ptt_bn_update_running_f32", "ptt_xcorr_z0_f32", "ptt_xcorr_z0_stat_chunks", "ptt_xcorr_z0_stats_f32", "ptt_xcorr_z0_bnbwd_f32", "ptt_xcorr_z0_bwd_workspace", "ptt_xcorr_z0_bwd_f32",
-    "ptt_bn_stats_train_f32", "ptt_bn_finish_partials_train_f32", "ptt_pack_weights_f32",
-    "ptt_sa_z0_rows_f32",
-    "ptt_row_jobs_f32", "ptt_point_jobs_f32", "ptt_fps_ball_knn_f32", "ptt_crop_compact_host_f32", "ptt_crop_regularize_f32", "ptt_colsum_workspace", "ptt_colsum_f32", "ptt_rows_gemm_pool_supported", "ptt_rows_gemm_pool_f32", "ptt_pool_select_f32", "ptt_sa_z0_rows_stat_chunks", "ptt_sa_z0_rows_stats_f32",
-    "ptt_track_losses_f32", "ptt_track_losses_bwd_f32", "ptt_adam_chunk_elems", "ptt_adam_clip_step_f32", "ptt_adam_clip_step_dev_f32",
-    "ptt_linear_wgrad_partials_f32", "ptt_linear_wgrad2_partials_f32", "ptt_colsum_partials_f32", "ptt_grad_finish_f32",
-    "ptt_rows_gemm_rsum16_supported", "ptt_rows_gemm_rsum16_f32", "ptt_scatter_rows_csr_sub_f32",
-    "ptt_unit_rows_f32", "ptt_cos_bwd_rows_f32", "ptt_track_select_update", "ptt_sa_z0_bnbwd_workspace", "ptt_sa_compact_workspace", "ptt_sa_z0_bnbwd_f32",
-    "ptt_layernorm_train_fwd_f32", "ptt_layernorm_bwd_workspace", "ptt_layernorm_bwd_f32",
-    "ptt_rows_gemm_rsum16_heads_supported", "ptt_rows_gemm_rsum16_heads_f32",
-]
-PTT_MAX_SEGMENTS = 4
+def _strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def parse_defines(text):
+    """{name: value} of every `#define PTT_NAME <decimal integer>` of a header text."""
+    return {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PTT_\w+)[ \t]+(-?\d+)[ \t]*$", _strip_comments(text), re.M)}
+
+
+# the scalar types the C ABI uses; every pointer (structures included) is passed as c_void_p, which takes byref(structure), a
+# ctypes array, a device or host address and None
+CTYPES = {"int": c_int, "int32_t": c_int32, "uint32_t": c_uint32, "int64_t": c_int64, "long long": c_longlong, "size_t": c_size_t,
+          "float": c_float, "double": c_double, "ptt_stream_t": c_void_p}
+
+
+def _ctype(decl, name, is_return=False):
+    words = decl.replace("*", " * ").split()
+    if not is_return and len(words) > 1 and words[-1] != "*":
+        words.pop()                                               # the parameter's name
+    if "*" in words:
+        if not is_return:
+            return c_void_p
+        if words == ["const", "char", "*"]:
+            return c_char_p
+    base = " ".join(w for w in words if w != "const")
+    if base not in CTYPES:
+        raise RuntimeError("ptt_amd: %s of %s in include/ptt_hip.h has the type '%s', which ptt_amd/_lib.py does not map to ctypes"
+                           % ("the return value" if is_return else "parameter '%s'" % decl.strip(), name, base))
+    return CTYPES[base]
+
+
+def parse_prototypes(text):
+    """{name: (restype, [argtypes])} of every function a header text declares, in its order. The header is plain C: one
+    prototype per `;`, `(void)` for no parameters; preprocessor lines, typedefs and the bodies of enums / structures are skipped.
+    A statement that is none of these, or a type outside CTYPES, raises."""
+    text = re.sub(r"^[ \t]*#.*$", " ", _strip_comments(text), flags=re.M).replace('extern "C" {', " ")
+    text = re.sub(r"\{[^{}]*\}", " ", text)
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split()).lstrip("} ")
+        if not stmt or stmt.split()[0] in ("typedef", "enum", "struct"):
+            continue
+        m = re.fullmatch(r"(.+?)\b(\w+) ?\((.*)\)", stmt)
+        if m is None:
+            raise RuntimeError("ptt_amd: cannot read '%s' in include/ptt_hip.h as a function prototype" % stmt)
+        ret, name, params = m.groups()
+        params = [] if params.strip() == "void" else params.split(",")
+        protos[name] = (_ctype(ret, name, is_return=True), [_ctype(p, name) for p in params])
+    return protos
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError("ptt_amd: %s is missing — the Python binding takes every prototype and constant of the C ABI from it" % HEADER_PATH)
+    with open(HEADER_PATH) as fh:
+        return fh.read()
+
+
+_header = _read_header()
+PROTOTYPES = parse_prototypes(_header)      # what lib() applies as restype / argtypes
+EXPORTS = list(PROTOTYPES)                  # every symbol include/ptt_hip.h declares (tests check the library exports all of them)
+DEFINES = parse_defines(_header)
+ABI_VERSION = DEFINES["PTT_ABI_VERSION"]
+PTT_SA_MAX_LAYERS = DEFINES["PTT_SA_MAX_LAYERS"]
+PTT_MAX_SEGMENTS = DEFINES["PTT_MAX_SEGMENTS"]
+PTT_CROP_JOBS_BY_VALUE_MAX = DEFINES["PTT_CROP_JOBS_BY_VALUE_MAX"]
 
 
 class CropJob(Structure):
@@ -67,6 +96,10 @@ class RegularizeJob(Structure):
                 ("seg_capacity", c_int32 * PTT_MAX_SEGMENTS), ("out", c_void_p), ("info", c_void_p),
                 ("n_seg", c_int32), ("input_size", c_int32)]
 
+
+class TrackBox(Structure):
+    """ptt_track_box: one tracklet's box in float64, quaternion (w, x, y, z); host memory."""
+    _fields_ = [("center", c_double * 3), ("wlh", c_double * 3), ("quat", c_double * 4)]
 
 
 class BnTrainTail(Structure):
@@ -176,153 +209,6 @@ class AttnDesc(Structure):
 _lib = None
 
 
-def _declare(lib):
-    vp, i, f = c_void_p, c_int, c_float
-    lib.ptt_version.restype = c_int
-    lib.ptt_error_name.restype = c_char_p
-    lib.ptt_error_name.argtypes = [i]
-    lib.ptt_last_error_string.restype = c_char_p
-    sigs = {
-        "ptt_fps_f32": [vp, i, i, i, vp, vp],
-        "ptt_fps_ws_f32": [vp, i, i, i, vp, vp, c_size_t, vp],
-        "ptt_spatial_order_f32": [vp, i, i, vp, vp],
-        "ptt_ball_query_grid_f32": [vp, vp, i, i, i, f, i, vp, vp, c_size_t, vp],
-        "ptt_centres_ball_query_grid_f32": [vp, vp, i, i, i, f, i, vp, vp, vp, vp, c_size_t, vp],
-        "ptt_gather_f32": [vp, vp, i, i, i, i, vp, vp],
-        "ptt_gather_grad_f32": [vp, vp, i, i, i, i, vp, vp],
-        "ptt_select_centres_f32": [vp, vp, i, i, i, vp, vp, vp],
-        "ptt_ball_query_f32": [vp, vp, i, i, i, f, i, vp, vp],
-        "ptt_centres_ball_query_f32": [vp, vp, i, i, i, f, i, vp, vp, vp, vp],
-        "ptt_group_f32": [vp, vp, i, i, i, i, i, vp, vp],
-        "ptt_group_grad_f32": [vp, vp, i, i, i, i, i, vp, vp],
-        "ptt_scatter_add_det_f32": [vp, vp, i, i, i, i, vp, vp, c_size_t, vp],
-        "ptt_knn_f32": [vp, i, i, i, vp, vp],
-        "ptt_knn_rel_f32": [vp, i, i, i, vp, vp, vp],
-        "ptt_pack_weight_f32": [vp, i, i, vp, vp],
-        "ptt_pack_weight_rot_f32": [vp, i, i, i, vp, vp],
-        "ptt_linear_f32": [vp, i, i, i, vp, i, vp, vp, i, vp, i, vp, i, vp],
-        "ptt_sa_fused_fwd_f32": [POINTER(SaDesc), vp],
-        "ptt_rows_mlp_f32": [vp, i, i, i, POINTER(SaLayer), i, vp, i, vp, i, vp],
-        "ptt_xcorr_fused_fwd_f32": [POINTER(XcorrDesc), vp],
-        "ptt_cosine_map_f32": [vp, c_int64, c_int64, c_int64, vp, c_int64, c_int64, c_int64, i, i, i, i, f, vp, vp],
-        "ptt_pt_attn_pair_f32": [POINTER(AttnDesc), vp],
-        "ptt_crop_compact_f32": [vp, i, vp],
-        "ptt_crop_compact_host_f32": [vp, i, vp],
-        "ptt_crop_regularize_f32": [vp, vp, i, vp, i, vp],
-        "ptt_colsum_f32": [vp, i, i, i, vp, vp, c_size_t, vp],
-        "ptt_rows_gemm_pool_supported": [i, i, i, i, i],
-        "ptt_rows_gemm_pool_f32": [vp, i, i, i, vp, vp, vp, i, vp, i, vp, c_size_t, i, vp, vp, vp, vp, vp],
-        "ptt_pool_select_f32": [vp, vp, vp, vp, vp, vp, i, i, vp, vp, vp],
-        "ptt_sa_z0_rows_stat_chunks": [i, i, i, i],
-        "ptt_sa_z0_rows_stats_f32": [vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, vp, vp, vp, c_size_t, vp],
-        "ptt_track_losses_f32": [vp, vp, vp, vp],
-        "ptt_track_losses_bwd_f32": [vp, vp, vp, vp, vp, vp, vp],
-        "ptt_adam_clip_step_f32": [vp, vp, vp, i, vp, vp, c_size_t, vp, vp],
-        "ptt_adam_clip_step_dev_f32": [vp, vp, vp, i, vp, i, vp, c_size_t, vp, vp],
-        "ptt_unit_rows_f32": [vp, c_longlong, c_longlong, c_longlong, i, i, i, f, vp, vp, vp],
-        "ptt_cos_bwd_rows_f32": [vp, vp, vp, vp, vp, c_longlong, c_longlong, c_longlong, i, i, i, i, vp, c_longlong, c_longlong, c_longlong, vp],
-        "ptt_track_select_update": [vp, i, vp, vp, i, i, vp, vp, vp],
-        "ptt_regularize_f32": [vp, i, vp, i, vp],
-        "ptt_mt19937_fill": [c_uint32, vp, i],
-        "ptt_select_box_f32": [vp, i, i, vp, vp, vp],
-        "ptt_track_crop_bounds": [vp, i, c_double, c_double, vp, vp, i],
-        "ptt_track_box_by_offset": [vp, i, vp, i, i, vp, vp],
-        "ptt_bn_stats_f32": [vp, i, i, i, f, vp, vp, vp, vp, c_size_t, vp],
-        "ptt_bn_apply_f32": [vp, i, vp, vp, vp, vp, i, i, i, vp, i, vp],
-        "ptt_bn_bwd_f32": [vp, i, vp, i, vp, i, vp, vp, vp, i, i, i, vp, i, vp, vp, vp, c_size_t, vp, vp, vp],
-        "ptt_bn_sums_f64": [vp, i, i, i, vp, vp, c_size_t, vp],
-        "ptt_bn_finish_f64": [vp, i, f, vp, vp, vp, vp],
-        "ptt_bn_bwd_sums_f64": [vp, i, vp, i, vp, i, vp, vp, i, i, vp, vp, c_size_t, vp, vp, vp],
-        "ptt_bn_bwd_apply_f32": [vp, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, i, i, vp, i, vp, vp, vp],
-        "ptt_pool_rows_f32": [vp, i, i, i, i, vp, i, vp, vp, vp, vp],
-        "ptt_linear_act_in_f32": [vp, i, i, i, vp, vp, vp, i, vp, i, vp],
-        "ptt_pool_rows_bwd_f32": [vp, i, vp, i, i, i, vp, i, vp],
-        "ptt_linear_wgrad_f32": [vp, i, vp, i, i, i, i, vp, i, vp, c_size_t, vp, vp, vp],
-        "ptt_pack_weight_strided_f32": [vp, i, i, c_int64, c_int64, i, c_int64, vp, vp],
-        "ptt_linear_batched_f32": [vp, i, i, i, c_int64, vp, c_int64, i, vp, vp, i, vp, i, c_int64, vp, i, c_int64, i, vp],
-        "ptt_softmax_rows_f32": [vp, c_int64, i, i, f, vp],
-        "ptt_layernorm_f32": [vp, i, i, i, vp, vp, f, vp, i, vp, i, vp],
-        "ptt_gather_rows_f32": [vp, vp, i, i, i, i, vp, vp],
-        "ptt_scatter_csr_i32": [vp, i, i, i, vp, vp, vp],
-        "ptt_scatter_rows_csr_f32": [vp, vp, vp, i, i, i, i, vp, vp],
-        "ptt_pt_pair_input_f32": [vp, vp, vp, vp, i, i, i, i, vp, vp],
-        "ptt_pt_attn_train_fwd_f32": [vp, vp, vp, vp, i, i, i, i, f, vp, vp, vp],
-        "ptt_pt_attn_train_bwd_f32": [vp, vp, vp, vp, vp, i, i, i, i, f, vp, vp, vp],
-        "ptt_rows_gemm_supported": [i, i, i, i, i],
-        "ptt_rows_gemm_stat_chunks": [i, i, i],
-        "ptt_rows_gemm_f32": [vp, i, i, i, vp, vp, vp, i, vp, i, vp, i, vp, i, vp, c_size_t, vp],
-        "ptt_rows_gemm_masked_f32": [vp, i, i, i, vp, i, vp, i, vp, i, vp, c_size_t, vp],
-        "ptt_bn_finish_partials_f32": [vp, i, i, i, f, vp, vp, vp, vp],
-        "ptt_bn_sums_partials_f64": [vp, i, i, i, vp, vp],
-        "ptt_linear_wgrad2_f32": [vp, i, vp, i, i, i, i, vp, i, vp, c_size_t, vp, vp, vp],
-        "ptt_linear_wgrad_partials_f32": [vp, i, vp, i, i, i, i, vp, c_size_t, vp, vp, vp, vp],
-        "ptt_linear_wgrad2_partials_f32": [vp, i, vp, i, i, i, i, vp, c_size_t, vp, vp, vp, vp],
-        "ptt_colsum_partials_f32": [vp, i, i, i, vp, c_size_t, vp, vp],
-        "ptt_grad_finish_f32": [vp, vp, vp, i, vp, vp],
-        "ptt_rows_gemm_rsum16_supported": [i, i, i, i],
-        "ptt_rows_gemm_rsum16_f32": [vp, i, i, i, vp, i, vp, i, vp, i, vp, i, vp, i, vp],
-        "ptt_rows_gemm_rsum16_heads_supported": [i, i, i, i],
-        "ptt_rows_gemm_rsum16_heads_f32": [vp, i, i, i, i, vp, vp, i, vp, i, vp, i, vp, i, vp],
-        "ptt_layernorm_train_fwd_f32": [vp, i, i, i, vp, vp, f, vp, i, vp, i, vp, vp, vp],
-        "ptt_layernorm_bwd_f32": [vp, i, vp, i, vp, vp, vp, i, i, vp, i, vp, vp, vp, c_size_t, vp],
-        "ptt_scatter_rows_csr_sub_f32": [vp, vp, vp, i, i, i, i, vp, vp, vp],
-        "ptt_rows_gemm_bnbwd_f32": [vp, i, i, i, vp, i, vp, i, vp, vp, vp, vp, vp, i, vp, c_size_t, vp],
-        "ptt_bn_bwd_from_partials_f32": [vp, i, vp, i, vp, i, vp, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp],
-        "ptt_bn_bwd_consts_f32": [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp],
-        "ptt_bn_bwd_pooled_consts_f32": [vp, i, vp, i, vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, c_size_t, vp, vp, vp],
-        "ptt_rows_gemm_bnbwd_fused_supported": [i, i, i, i],
-        "ptt_rows_gemm_bnbwd_fused_f32": [POINTER(BnBwdInput), i, i, vp, i, vp, i, vp, vp, vp, vp, vp, i, vp, c_size_t, vp],
-        "ptt_bn_bwd_sums_partials_f64": [vp, i, i, vp, vp],
-        "ptt_pt_pair_input_ld_f32": [vp, i, vp, i, vp, vp, i, i, i, i, vp, vp],
-        "ptt_pt_attn_fwd_ld_f32": [vp, vp, i, vp, vp, i, i, i, i, f, vp, vp, vp],
-        "ptt_bn_update_running_f32": [vp, vp, vp, f, i, vp, vp, vp, vp],
-        "ptt_bn_stats_train_f32": [vp, i, i, i, f, vp, vp, vp, vp, c_size_t, vp, vp],
-        "ptt_bn_finish_partials_train_f32": [vp, i, i, i, f, vp, vp, vp, vp, vp],
-        "ptt_pack_weights_f32": [vp, i, vp, vp],
-        "ptt_sa_z0_rows_f32": [vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, vp, vp, vp],
-        "ptt_xcorr_z0_f32": [vp, vp, vp, i, i, i, i, vp, vp],
-        "ptt_xcorr_z0_stat_chunks": [i, i, i, i],
-        "ptt_sa_z0_bnbwd_f32": [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, c_longlong, i, vp, vp, vp, vp, vp, c_size_t, vp],
-        "ptt_xcorr_z0_bnbwd_f32": [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, c_size_t, vp],
-        "ptt_xcorr_z0_stats_f32": [vp, vp, vp, i, i, i, i, vp, vp, c_size_t, vp],
-        "ptt_xcorr_z0_bwd_f32": [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, c_size_t, vp],
-        "ptt_bn_bwd_pooled_f32": [vp, i, vp, i, vp, i, vp, vp, vp, i, i, vp, i, vp, vp, vp, c_size_t, vp, vp, vp],
-        "ptt_bn_bwd_pooled_sums_f64": [vp, i, vp, i, vp, i, vp, vp, i, i, vp, vp, c_size_t, vp, vp, vp],
-        "ptt_bn_bwd_pooled_apply_f32": [vp, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, i, i, vp, i, vp, vp, vp],
-        "ptt_row_jobs_f32": [POINTER(RowJob), i, vp],
-        "ptt_point_jobs_f32": [POINTER(PointJob), i, vp],
-        "ptt_fps_ball_knn_f32": [vp, i, i, i, f, i, i, vp, vp, vp, vp, vp, vp, vp],
-    }
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.restype = c_int
-        fn.argtypes = args
-    lib.ptt_packed_weight_elems.restype = c_size_t
-    lib.ptt_packed_weight_elems.argtypes = [i, i]
-    lib.ptt_scatter_add_det_workspace.restype = c_size_t
-    lib.ptt_scatter_add_det_workspace.argtypes = [i, i, i]
-    lib.ptt_ball_query_grid_workspace.restype = c_size_t
-    lib.ptt_ball_query_grid_workspace.argtypes = [i, i]
-    lib.ptt_bn_stats_workspace.restype = c_size_t
-    lib.ptt_bn_stats_workspace.argtypes = [i, i]
-    lib.ptt_linear_wgrad_workspace.restype = c_size_t
-    lib.ptt_linear_wgrad_workspace.argtypes = [i, i, i]
-    lib.ptt_xcorr_z0_bwd_workspace.restype = c_size_t
-    lib.ptt_xcorr_z0_bwd_workspace.argtypes = [i, i, i]
-    lib.ptt_sa_z0_bnbwd_workspace.restype = c_size_t
-    lib.ptt_sa_z0_bnbwd_workspace.argtypes = [c_longlong, i]
-    lib.ptt_sa_compact_workspace.restype = c_size_t
-    lib.ptt_sa_compact_workspace.argtypes = [i, i]
-    lib.ptt_adam_chunk_elems.restype = c_int
-    lib.ptt_adam_chunk_elems.argtypes = []
-    lib.ptt_layernorm_bwd_workspace.restype = c_size_t
-    lib.ptt_layernorm_bwd_workspace.argtypes = [i, i]
-    lib.ptt_colsum_workspace.restype = c_size_t
-    lib.ptt_colsum_workspace.argtypes = [i, i]
-    lib.ptt_linear_wgrad2_workspace.restype = c_size_t
-    lib.ptt_linear_wgrad2_workspace.argtypes = [i, i, i]
-
-
 def lib():
     """Load libptt_hip.so once. Raises RuntimeError (never falls back) when it is absent."""
     global _lib
@@ -338,7 +224,9 @@ def lib():
             loaded = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # e.g. no ROCm runtime on this host
             raise RuntimeError("ptt_amd: cannot load %s: %s" % (LIB_PATH, e))
-        _declare(loaded)
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(loaded, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if loaded.ptt_version() != ABI_VERSION:
             raise RuntimeError("ptt_amd: %s has ABI version %d, this package expects %d — rebuild it with "
                                "`python -m ptt_amd.build`" % (LIB_PATH, loaded.ptt_version(), ABI_VERSION))

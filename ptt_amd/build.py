@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ptt_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "ptt_amd", "lib")
 LIB = os.path.join(LIBDIR, "libptt_hip.so")
+HEADER = os.path.join(ROOT, "include", "ptt_hip.h")        # the C ABI: compiled against here, bound from by _lib.py
 
 HIP_SOURCES = ["errors.hip", "point_ops.hip", "mfma_ops.hip", "track_ops.hip", "train_ops.hip", "gemm_ops.hip", "rowjobs.hip", "step_ops.hip", "wgrad_stream.hip"]
 # FPS / ball query / kNN index parity needs un-fused fp32 arithmetic (see point_ops.hip header)
@@ -48,7 +49,7 @@ def build_hip(force=False, verbose=False):
                 os.remove(path)
     os.makedirs(LIBDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers.append(os.path.join(ROOT, "include", "ptt_hip.h"))
+    headers.append(HEADER)
     objs, running = [], []
     for src in HIP_SOURCES:
         s = os.path.join(CSRC, src)

@@ -6,6 +6,7 @@ The first group has the names, argument order and error behaviour of the third-p
 fp32 / int32, contiguous. Kernels are enqueued on the current torch stream; nothing
 synchronises. The second group exposes the fused fp32-MFMA kernels.
 """
+import contextlib
 import ctypes
 import os
 
@@ -158,6 +159,35 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+_UNTIMED = contextlib.nullcontext()
+
+
+def _launch(name, device, *args, timed=None):
+    """Enqueue the entry point `name` of the C ABI on `device`: inside its device context, with the current torch stream (read
+    now) appended as the last argument; a non-zero status raises (_lib.check). timed: the name start_kernel_timing() knows
+    this launch by."""
+    with torch.cuda.device(device), (_timed(timed) if timed else _UNTIMED):
+        rc = getattr(_lib.lib(), name)(*args, _stream())
+    if rc:
+        _lib.check(rc, name)
+
+
+def _host(name, *args):
+    """A host-only entry point (no stream, no device work): -> what it returns — a size, a count, a flag or a status."""
+    return getattr(_lib.lib(), name)(*args)
+
+
+def _host_checked(name, *args):
+    _lib.check(_host(name, *args), name)
+
+
+def _workspace(query, device, *dims):
+    """The workspace a launch asks for through its ptt_*_workspace(dims) query: -> (tensor, (pointer, bytes)), the pair being the
+    two arguments the launch takes."""
+    ws = _ws(_host(query, *dims), device)
+    return ws, (_ptr(ws), ws.numel() * 8)
+
+
 # --------------------------------------------------------------------------- _ext-compatible ops
 FPS_RESIDENT_MAX_N, FPS_RESIDENT_MAX_NPOINT = 16384, 15360         # ptt_fps_f32's register / LDS-resident reach
 
@@ -167,13 +197,11 @@ def furthest_point_sampling(xyz, npoint):
     _chk(xyz, "xyz", torch.float32, 3)
     B, N, _ = xyz.shape
     out = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device)
-    with torch.cuda.device(xyz.device), _timed('ptt_fps_f32'):
-        if N <= FPS_RESIDENT_MAX_N and int(npoint) <= FPS_RESIDENT_MAX_NPOINT:
-            _lib.check(_lib.lib().ptt_fps_f32(_ptr(xyz), B, N, int(npoint), _ptr(out), _stream()), "ptt_fps_f32")
-        else:           # the reference's op has no size limit: min-distances in a workspace, identical picks, slower
-            ws = torch.empty((B * N,), dtype=torch.float32, device=xyz.device)
-            _lib.check(_lib.lib().ptt_fps_ws_f32(_ptr(xyz), B, N, int(npoint), _ptr(out), _ptr(ws), ws.numel(), _stream()),
-                       "ptt_fps_ws_f32")
+    if N <= FPS_RESIDENT_MAX_N and int(npoint) <= FPS_RESIDENT_MAX_NPOINT:
+        _launch("ptt_fps_f32", xyz.device, _ptr(xyz), B, N, int(npoint), _ptr(out), timed='ptt_fps_f32')
+    else:           # the reference's op has no size limit: min-distances in a workspace, identical picks, slower
+        ws = torch.empty((B * N,), dtype=torch.float32, device=xyz.device)
+        _launch("ptt_fps_ws_f32", xyz.device, _ptr(xyz), B, N, int(npoint), _ptr(out), _ptr(ws), ws.numel(), timed='ptt_fps_f32')
     return out
 
 
@@ -184,9 +212,7 @@ def gather_points(features, idx):
     B, C, N = features.shape
     M = idx.shape[1]
     out = torch.empty((B, C, M), dtype=torch.float32, device=features.device)
-    with torch.cuda.device(features.device):
-        _lib.check(_lib.lib().ptt_gather_f32(_ptr(features), _ptr(idx), B, C, N, M, _ptr(out), _stream()),
-                   "ptt_gather_f32")
+    _launch("ptt_gather_f32", features.device, _ptr(features), _ptr(idx), B, C, N, M, _ptr(out))
     return out
 
 
@@ -195,11 +221,9 @@ def scatter_add_det(src, idx, N):
     src (B,C,E) f32, idx (B,E) i32 -> (B,C,N); E <= 16384."""
     B, C, E = src.shape
     out = torch.empty((B, C, int(N)), dtype=torch.float32, device=src.device)
-    nbytes = _lib.lib().ptt_scatter_add_det_workspace(B, int(N), E)
+    nbytes = _host("ptt_scatter_add_det_workspace", B, int(N), E)
     ws = torch.empty((max(1, (nbytes + 3) // 4),), dtype=torch.int32, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().ptt_scatter_add_det_f32(_ptr(src), _ptr(idx), B, C, int(N), E, _ptr(out), _ptr(ws),
-                                                      ws.numel() * 4, _stream()), "ptt_scatter_add_det_f32")
+    _launch("ptt_scatter_add_det_f32", src.device, _ptr(src), _ptr(idx), B, C, int(N), E, _ptr(out), _ptr(ws), ws.numel() * 4)
     return out
 
 
@@ -232,9 +256,7 @@ def gather_points_grad(grad_out, idx, N):
     if M > 0 and _det_grads(M, N):
         return scatter_add_det(grad_out, idx, N)
     out = torch.empty((B, C, int(N)), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        _lib.check(_lib.lib().ptt_gather_grad_f32(_ptr(grad_out), _ptr(idx), B, C, int(N), M, _ptr(out), _stream()),
-                   "ptt_gather_grad_f32")
+    _launch("ptt_gather_grad_f32", grad_out.device, _ptr(grad_out), _ptr(idx), B, C, int(N), M, _ptr(out))
     return out
 
 
@@ -247,9 +269,7 @@ def select_centres(xyz, idx, npoint, want_idx64=True):
         _chk(idx, "idx", torch.int32, 2)
     new_xyz = torch.empty((B, int(npoint), 3), dtype=torch.float32, device=xyz.device)
     idx64 = torch.empty((B, int(npoint)), dtype=torch.int64, device=xyz.device) if (want_idx64 and idx is not None) else None
-    with torch.cuda.device(xyz.device):
-        _lib.check(_lib.lib().ptt_select_centres_f32(_ptr(xyz), _ptr(idx), B, N, int(npoint), _ptr(new_xyz), _ptr(idx64),
-                                                     _stream()), "ptt_select_centres_f32")
+    _launch("ptt_select_centres_f32", xyz.device, _ptr(xyz), _ptr(idx), B, N, int(npoint), _ptr(new_xyz), _ptr(idx64))
     return new_xyz, idx64
 
 
@@ -263,14 +283,13 @@ def ball_query(new_xyz, xyz, radius, nsample):
     B, M, _ = new_xyz.shape
     N = xyz.shape[1]
     out = torch.empty((B, M, int(nsample)), dtype=torch.int32, device=xyz.device)
-    with torch.cuda.device(xyz.device), _timed('ptt_ball_query_f32'):
-        if GRID_BALL_QUERY_MIN_POINTS <= N <= 131072:          # large clouds: 27 cells of a uniform grid instead of the whole cloud
-            ws = _ws(_lib.lib().ptt_ball_query_grid_workspace(B, N), xyz.device)
-            _lib.check(_lib.lib().ptt_ball_query_grid_f32(_ptr(new_xyz), _ptr(xyz), B, M, N, float(radius), int(nsample), _ptr(out),
-                                                          _ptr(ws), ws.numel() * 8, _stream()), "ptt_ball_query_grid_f32")
-        else:
-            _lib.check(_lib.lib().ptt_ball_query_f32(_ptr(new_xyz), _ptr(xyz), B, M, N, float(radius), int(nsample),
-                                                     _ptr(out), _stream()), "ptt_ball_query_f32")
+    if GRID_BALL_QUERY_MIN_POINTS <= N <= 131072:          # large clouds: 27 cells of a uniform grid instead of the whole cloud
+        ws, ws_arg = _workspace("ptt_ball_query_grid_workspace", xyz.device, B, N)
+        _launch("ptt_ball_query_grid_f32", xyz.device, _ptr(new_xyz), _ptr(xyz), B, M, N, float(radius), int(nsample), _ptr(out), *ws_arg,
+                timed='ptt_ball_query_f32')
+    else:
+        _launch("ptt_ball_query_f32", xyz.device, _ptr(new_xyz), _ptr(xyz), B, M, N, float(radius), int(nsample), _ptr(out),
+                timed='ptt_ball_query_f32')
     return out
 
 
@@ -285,15 +304,13 @@ def centres_ball_query(xyz, sel, npoint, radius, nsample, want_idx64=True):
     new_xyz = torch.empty((B, M, 3), dtype=torch.float32, device=xyz.device)
     idx64 = torch.empty((B, M), dtype=torch.int64, device=xyz.device) if (want_idx64 and sel is not None) else None
     idx = torch.empty((B, M, int(nsample)), dtype=torch.int32, device=xyz.device)
-    with torch.cuda.device(xyz.device), _timed('ptt_ball_query_f32'):
-        if GRID_BALL_QUERY_MIN_POINTS <= N <= 131072:
-            ws = _ws(_lib.lib().ptt_ball_query_grid_workspace(B, N), xyz.device)
-            _lib.check(_lib.lib().ptt_centres_ball_query_grid_f32(_ptr(xyz), _ptr(sel), B, N, M, float(radius), int(nsample), _ptr(new_xyz),
-                                                                  _ptr(idx64), _ptr(idx), _ptr(ws), ws.numel() * 8, _stream()),
-                       "ptt_centres_ball_query_grid_f32")
-        else:
-            _lib.check(_lib.lib().ptt_centres_ball_query_f32(_ptr(xyz), _ptr(sel), B, N, M, float(radius), int(nsample), _ptr(new_xyz),
-                                                             _ptr(idx64), _ptr(idx), _stream()), "ptt_centres_ball_query_f32")
+    if GRID_BALL_QUERY_MIN_POINTS <= N <= 131072:
+        ws, ws_arg = _workspace("ptt_ball_query_grid_workspace", xyz.device, B, N)
+        _launch("ptt_centres_ball_query_grid_f32", xyz.device, _ptr(xyz), _ptr(sel), B, N, M, float(radius), int(nsample), _ptr(new_xyz), _ptr(idx64),
+                _ptr(idx), *ws_arg, timed='ptt_ball_query_f32')
+    else:
+        _launch("ptt_centres_ball_query_f32", xyz.device, _ptr(xyz), _ptr(sel), B, N, M, float(radius), int(nsample), _ptr(new_xyz), _ptr(idx64),
+                _ptr(idx), timed='ptt_ball_query_f32')
     return new_xyz, idx64, idx
 
 
@@ -304,9 +321,7 @@ def group_points(features, idx):
     B, C, N = features.shape
     _, M, ns = idx.shape
     out = torch.empty((B, C, M, ns), dtype=torch.float32, device=features.device)
-    with torch.cuda.device(features.device):
-        _lib.check(_lib.lib().ptt_group_f32(_ptr(features), _ptr(idx), B, C, N, M, ns, _ptr(out), _stream()),
-                   "ptt_group_f32")
+    _launch("ptt_group_f32", features.device, _ptr(features), _ptr(idx), B, C, N, M, ns, _ptr(out))
     return out
 
 
@@ -318,9 +333,7 @@ def group_points_grad(grad_out, idx, N):
     if M * ns > 0 and _det_grads(M * ns, N):
         return scatter_add_det(grad_out.view(B, C, M * ns), idx.view(B, M * ns), N)
     out = torch.empty((B, C, int(N)), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        _lib.check(_lib.lib().ptt_group_grad_f32(_ptr(grad_out), _ptr(idx), B, C, int(N), M, ns, _ptr(out),
-                                                 _stream()), "ptt_group_grad_f32")
+    _launch("ptt_group_grad_f32", grad_out.device, _ptr(grad_out), _ptr(idx), B, C, int(N), M, ns, _ptr(out))
     return out
 
 
@@ -346,8 +359,7 @@ def knn(xyz, k, want_rel=False):
     B, N, _ = xyz.shape
     out = torch.empty((B, N, int(k)), dtype=torch.int32, device=xyz.device)
     rel = torch.empty((B, N, int(k), 3), dtype=torch.float32, device=xyz.device) if want_rel else None
-    with torch.cuda.device(xyz.device), _timed('ptt_knn_f32'):
-        _lib.check(_lib.lib().ptt_knn_rel_f32(_ptr(xyz), B, N, int(k), _ptr(out), _ptr(rel), _stream()), "ptt_knn_rel_f32")
+    _launch("ptt_knn_rel_f32", xyz.device, _ptr(xyz), B, N, int(k), _ptr(out), _ptr(rel), timed='ptt_knn_f32')
     return (out, rel) if want_rel else out
 
 
@@ -359,11 +371,9 @@ def pack_weight(weight, rot=0):
     w = w.reshape(w.shape[0], -1).contiguous().float()
     _chk(w, "weight", torch.float32, 2)
     Cout, K = w.shape
-    n = _lib.lib().ptt_packed_weight_elems(Cout, K)
+    n = _host("ptt_packed_weight_elems", Cout, K)
     out = torch.empty((n,), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(_lib.lib().ptt_pack_weight_rot_f32(_ptr(w), Cout, K, int(rot), _ptr(out), _stream()),
-                   "ptt_pack_weight_rot_f32")
+    _launch("ptt_pack_weight_rot_f32", w.device, _ptr(w), Cout, K, int(rot), _ptr(out))
     return out
 
 
@@ -395,11 +405,9 @@ def linear(x, wpacked, cout, scale=None, shift=None, relu=False, residual=None, 
     # except 256-column layers of 6144+ rows (fc2 and cov_final of 48 frames), which the row GEMM's 128-column workgroups of
     # round 5 take faster: 6144 x 512 -> 256 18.7 vs 25.2 us, 6144 x 256 -> 256 11.1 vs 14.3 (1536 or 128 columns, 3072 rows: slower)
     if (scale is None and (rows > 8192 or (rows >= 6144 and int(cout) == 256)) and x2.data_ptr() % 16 == 0 and o2.is_contiguous()
-            and _lib.lib().ptt_rows_gemm_supported(rows, K, int(cout), x2.stride(0), int(cout))):
-        with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
-            _lib.check(_lib.lib().ptt_rows_gemm_f32(_ptr(x2), rows, K, x2.stride(0), None, None, _ptr(wpacked), int(cout), _ptr(shift),
-                                                    1 if relu else 0, _ptr(r2), r2.stride(0) if r2 is not None else int(cout),
-                                                    _ptr(o2), int(cout), None, 0, _stream()), "ptt_rows_gemm_f32")
+            and _host("ptt_rows_gemm_supported", rows, K, int(cout), x2.stride(0), int(cout))):
+        _launch("ptt_rows_gemm_f32", x.device, _ptr(x2), rows, K, x2.stride(0), None, None, _ptr(wpacked), int(cout), _ptr(shift), 1 if relu else 0,
+                _ptr(r2), r2.stride(0) if r2 is not None else int(cout), _ptr(o2), int(cout), None, 0, timed='ptt_linear_f32')
         return out
     # at most 1024 rows of >= 192 channels (the launches of ONE tracklet frame): K split over the waves of a workgroup
     # (ptt_row_jobs_f32) — 128 x 512 -> 512: 9.0 against 12.8 us, 1024 x 512 -> 512: 10.9 against 13.1
@@ -407,11 +415,9 @@ def linear(x, wpacked, cout, scale=None, shift=None, relu=False, residual=None, 
     if rows <= ROW_JOB_MAX_ROWS and 192 <= K <= 1024 and o2.stride(1) == 1:
         row_jobs([row_job(wpacked, cout, x=x2, scale=scale, shift=shift, act=1 if relu else 0, res=r2, out=o2)])
         return out
-    with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
-        _lib.check(_lib.lib().ptt_linear_f32(
-            _ptr(x2), rows, K, x2.stride(0) if rows > 1 else K, _ptr(wpacked), int(cout), _ptr(scale), _ptr(shift),
-            1 if relu else 0, _ptr(r2), (r2.stride(0) if (r2 is not None and rows > 1) else int(cout)),
-            _ptr(o2), o2.stride(0) if rows > 1 else int(cout), _stream()), "ptt_linear_f32")
+    _launch("ptt_linear_f32", x.device, _ptr(x2), rows, K, x2.stride(0) if rows > 1 else K, _ptr(wpacked), int(cout), _ptr(scale), _ptr(shift),
+            1 if relu else 0, _ptr(r2), (r2.stride(0) if (r2 is not None and rows > 1) else int(cout)), _ptr(o2),
+            o2.stride(0) if rows > 1 else int(cout), timed='ptt_linear_f32')
     return out
 
 
@@ -478,10 +484,9 @@ def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, 
             raise RuntimeError("compact workspace must be a contiguous tensor on %s" % xyz.device)
         d.compact_ws, d.compact_ws_bytes = compact.data_ptr(), compact.numel() * compact.element_size()
     elif compact:
-        ws = _ws(_lib.lib().ptt_sa_compact_workspace(B, M), xyz.device)
-        d.compact_ws, d.compact_ws_bytes = ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(xyz.device), _timed('ptt_sa_fused_fwd_f32'):
-        _lib.check(_lib.lib().ptt_sa_fused_fwd_f32(ctypes.byref(d), _stream()), "ptt_sa_fused_fwd_f32")
+        ws, (_, d.compact_ws_bytes) = _workspace("ptt_sa_compact_workspace", xyz.device, B, M)
+        d.compact_ws = ws.data_ptr()
+    _launch("ptt_sa_fused_fwd_f32", xyz.device, ctypes.byref(d), timed='ptt_sa_fused_fwd_f32')
     return out
 
 
@@ -498,10 +503,8 @@ def cosine_map(search_feats, templ_feats, eps=1e-8):
     out = torch.empty((B, Ns, Nt), dtype=torch.float32, device=search_feats.device)
     ssb, ssc, ssn = search_feats.stride()
     tsb, tsc, tsn = templ_feats.stride()
-    with torch.cuda.device(out.device), _timed('ptt_cosine_map_f32'):
-        _lib.check(_lib.lib().ptt_cosine_map_f32(search_feats.data_ptr(), ssb, ssn, ssc, templ_feats.data_ptr(), tsb, tsn,
-                                                 tsc, B, Ns, Nt, C, float(eps), out.data_ptr(), _stream()),
-                   "ptt_cosine_map_f32")
+    _launch("ptt_cosine_map_f32", out.device, search_feats.data_ptr(), ssb, ssn, ssc, templ_feats.data_ptr(), tsb, tsn, tsc, B, Ns, Nt, C, float(eps),
+            out.data_ptr(), timed='ptt_cosine_map_f32')
     return out
 
 
@@ -527,10 +530,8 @@ def rows_mlp(x, layers, residual=None):
         arr[i].scale = sc.data_ptr() if sc is not None else None
         arr[i].shift = sh.data_ptr() if sh is not None else None
         arr[i].Cin, arr[i].Cout, arr[i].relu = int(cin), int(co), int(bool(relu))
-    with torch.cuda.device(x.device), _timed('ptt_rows_mlp_f32'):
-        _lib.check(_lib.lib().ptt_rows_mlp_f32(_ptr(x2), rows, K, x2.stride(0), arr, len(layers), _ptr(res2),
-                                               res2.stride(0) if res2 is not None else 0, _ptr(out), cout, _stream()),
-                   "ptt_rows_mlp_f32")
+    _launch("ptt_rows_mlp_f32", x.device, _ptr(x2), rows, K, x2.stride(0), arr, len(layers), _ptr(res2), res2.stride(0) if res2 is not None else 0,
+            _ptr(out), cout, timed='ptt_rows_mlp_f32')
     return out.view(*x.shape[:-1], cout)
 
 
@@ -591,8 +592,7 @@ def xcorr_fused(search_feats, templ_feats, P, w_sim, scale0, shift0, layers, eps
         L.scale = sc.data_ptr() if sc is not None else None
         L.shift = sh.data_ptr() if sh is not None else None
         L.Cin, L.Cout, L.relu = int(cin), int(co), int(bool(relu))
-    with torch.cuda.device(P.device), _timed('ptt_xcorr_fused_fwd_f32'):
-        _lib.check(_lib.lib().ptt_xcorr_fused_fwd_f32(ctypes.byref(d), _stream()), "ptt_xcorr_fused_fwd_f32")
+    _launch("ptt_xcorr_fused_fwd_f32", P.device, ctypes.byref(d), timed='ptt_xcorr_fused_fwd_f32')
     return out, sim
 
 
@@ -608,8 +608,7 @@ def spatial_order(xyz):
     _chk(xyz, "xyz", torch.float32, 3)
     B, N, _ = xyz.shape
     order = torch.empty((B, N), dtype=torch.int32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        _lib.check(_lib.lib().ptt_spatial_order_f32(_ptr(xyz), B, N, _ptr(order), _stream()), "ptt_spatial_order_f32")
+    _launch("ptt_spatial_order_f32", xyz.device, _ptr(xyz), B, N, _ptr(order))
     return order
 
 
@@ -643,8 +642,7 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
         if tuple(order.shape) != (B, N):
             raise ValueError("order: (B,N) int32 expected")
         d.order = order.data_ptr()
-    with torch.cuda.device(xyz.device), _timed('ptt_pt_attn_pair_f32'):
-        _lib.check(_lib.lib().ptt_pt_attn_pair_f32(ctypes.byref(d), _stream()), "ptt_pt_attn_pair_f32")
+    _launch("ptt_pt_attn_pair_f32", xyz.device, ctypes.byref(d), timed='ptt_pt_attn_pair_f32')
     return res, attn
 
 
@@ -665,44 +663,32 @@ def layernorm(x, weight, bias, eps, residual=None, out=None):
         if r2.stride(1) != 1:
             r2 = r2.contiguous()
     rows = x2.shape[0]
-    with torch.cuda.device(x.device), _timed('ptt_layernorm_f32'):
-        _lib.check(_lib.lib().ptt_layernorm_f32(_ptr(x2), rows, C, x2.stride(0) if rows > 1 else C, _ptr(weight), _ptr(bias),
-                                                float(eps), _ptr(r2), (r2.stride(0) if (r2 is not None and rows > 1) else C),
-                                                _ptr(o2), o2.stride(0) if rows > 1 else C, _stream()), "ptt_layernorm_f32")
+    _launch("ptt_layernorm_f32", x.device, _ptr(x2), rows, C, x2.stride(0) if rows > 1 else C, _ptr(weight), _ptr(bias), float(eps), _ptr(r2),
+            (r2.stride(0) if (r2 is not None and rows > 1) else C), _ptr(o2), o2.stride(0) if rows > 1 else C, timed='ptt_layernorm_f32')
     return out
 
 
 # --------------------------------------------------------------------------- N4: tracking-loop pre/post-processing
 import numpy as np      # noqa: E402  (host-side job tables only)
 
-CROP_JOB = np.dtype([('points', '<u8'), ('ld', '<i8'), ('lo1', '<f8', 3), ('hi1', '<f8', 3), ('trans', '<f8', 3),
-                     ('rot', '<f8', 9), ('lo2', '<f8', 3), ('hi2', '<f8', 3), ('out', '<u8'), ('count', '<u8'),
-                     ('n_points', '<i4'), ('capacity', '<i4'), ('label_out', '<u8'), ('ltrans', '<f8', 3), ('lrot', '<f8', 9),
-                     ('llo', '<f8', 3), ('lhi', '<f8', 3), ('append', '<i4'), ('reserved', '<i4')])   # = ptt_crop_job, 392 bytes
-REGULARIZE_JOB = np.dtype([('seg', '<u8', 4), ('seg_count', '<u8', 4), ('seg_capacity', '<i4', 4), ('out', '<u8'),
-                           ('info', '<u8'), ('n_seg', '<i4'), ('input_size', '<i4')])   # = ptt_regularize_job, 104 bytes
-assert CROP_JOB.itemsize == ctypes.sizeof(_lib.CropJob) and REGULARIZE_JOB.itemsize == ctypes.sizeof(_lib.RegularizeJob)
-
-TRACK_BOX = np.dtype([('center', '<f8', 3), ('wlh', '<f8', 3), ('quat', '<f8', 4)])     # = ptt_track_box, 80 bytes
+# the host-side job tables are numpy arrays of the C structures themselves (one mirror per structure: _lib's)
+CROP_JOB, REGULARIZE_JOB, TRACK_BOX = np.dtype(_lib.CropJob), np.dtype(_lib.RegularizeJob), np.dtype(_lib.TrackBox)
 
 
 def track_crop_bounds(boxes, offset, scale, extra2, jobs, job_stride=1):
     """ptt_track_crop_bounds: the float64 crop quantities of crop_center_pc for every box (TRACK_BOX array) into the
     lo1/hi1/trans/rot/lo2/hi2 fields of jobs[i * job_stride] (a CROP_JOB array, typically a view of pinned memory)."""
     ex = None if extra2 is None else np.ascontiguousarray(extra2, np.float64)
-    _lib.check(_lib.lib().ptt_track_crop_bounds(boxes.ctypes.data, len(boxes), float(offset), float(scale),
-                                                ex.ctypes.data if ex is not None else None, jobs.ctypes.data,
-                                                int(job_stride)), "ptt_track_crop_bounds")
+    _host_checked("ptt_track_crop_bounds", boxes.ctypes.data, len(boxes), float(offset), float(scale), ex.ctypes.data if ex is not None else None,
+                  jobs.ctypes.data, int(job_stride))
 
 
 def track_box_by_offset(boxes, offsets, use_z, active=None, rng_pos=None):
     """ptt_track_box_by_offset: boxes[i] <- get_box_by_offset(boxes[i], offsets[i, 0:4], use_z) in place (TRACK_BOX array,
     float32 (n, >=4) C-contiguous offsets, optional int32 active mask and int64 generator positions)."""
     assert offsets.dtype == np.float32 and offsets.flags['C_CONTIGUOUS'] and offsets.shape[1] >= 4
-    _lib.check(_lib.lib().ptt_track_box_by_offset(boxes.ctypes.data, len(boxes), offsets.ctypes.data, offsets.shape[1],
-                                                  int(bool(use_z)), active.ctypes.data if active is not None else None,
-                                                  rng_pos.ctypes.data if rng_pos is not None else None),
-               "ptt_track_box_by_offset")
+    _host_checked("ptt_track_box_by_offset", boxes.ctypes.data, len(boxes), offsets.ctypes.data, offsets.shape[1], int(bool(use_z)),
+                  active.ctypes.data if active is not None else None, rng_pos.ctypes.data if rng_pos is not None else None)
 
 
 def track_select_update(proposals, info, boxes, use_z, active, rng_pos, est_out):
@@ -712,9 +698,8 @@ def track_select_update(proposals, info, boxes, use_z, active, rng_pos, est_out)
     P = proposals.shape[1] if proposals.ndim == 3 else 1
     assert proposals.dtype == np.float32 and proposals.flags['C_CONTIGUOUS'] and info.dtype == np.int32 and info.flags['C_CONTIGUOUS']
     assert est_out.dtype == np.float32 and est_out.shape == (B, 5) and est_out.flags['C_CONTIGUOUS'] and rng_pos.dtype == np.int64
-    rc = _lib.lib().ptt_track_select_update(proposals.ctypes.data, P, info.ctypes.data, boxes.ctypes.data, B, int(bool(use_z)),
-                                            active.ctypes.data if active is not None else None, rng_pos.ctypes.data, est_out.ctypes.data)
-    _lib.check(rc, "ptt_track_select_update")
+    _host_checked("ptt_track_select_update", proposals.ctypes.data, P, info.ctypes.data, boxes.ctypes.data, B, int(bool(use_z)),
+                  active.ctypes.data if active is not None else None, rng_pos.ctypes.data, est_out.ctypes.data)
 
 
 _mt_tables = {}
@@ -727,7 +712,7 @@ def mt19937_draws(device, n=8192, seed=1):
     key = (str(device), int(n), int(seed))
     if key not in _mt_tables:
         host = np.empty(int(n), np.uint32)
-        _lib.check(_lib.lib().ptt_mt19937_fill(int(seed), host.ctypes.data, int(n)), "ptt_mt19937_fill")
+        _host_checked("ptt_mt19937_fill", int(seed), host.ctypes.data, int(n))
         _mt_tables[key] = torch.from_numpy(host.view(np.int32)).to(device)
         publish_params(torch.device(device), replaced=False)
     return _mt_tables[key]
@@ -745,40 +730,33 @@ def upload_jobs(jobs, out=None):
 
 def crop_compact(jobs_dev, n_jobs):
     """ptt_crop_compact_f32 over a device-resident table of `n_jobs` ptt_crop_job records (uint8 tensor)."""
-    with torch.cuda.device(jobs_dev.device), _timed('ptt_crop_compact_f32'):
-        _lib.check(_lib.lib().ptt_crop_compact_f32(_ptr(jobs_dev), int(n_jobs), _stream()), "ptt_crop_compact_f32")
+    _launch("ptt_crop_compact_f32", jobs_dev.device, _ptr(jobs_dev), int(n_jobs), timed='ptt_crop_compact_f32')
 
 
-CROP_JOBS_BY_VALUE_MAX = 8
+CROP_JOBS_BY_VALUE_MAX = _lib.PTT_CROP_JOBS_BY_VALUE_MAX
 
 
 def crop_compact_host(jobs_np, n_jobs, device):
     """ptt_crop_compact_host_f32: the crops of a host-resident (numpy structured) job table, passed by value with the launch —
     at most CROP_JOBS_BY_VALUE_MAX jobs; the table may be rewritten as soon as this returns."""
-    with torch.cuda.device(device), _timed('ptt_crop_compact_f32'):
-        _lib.check(_lib.lib().ptt_crop_compact_host_f32(ctypes.c_void_p(jobs_np.ctypes.data), int(n_jobs), _stream()),
-                   "ptt_crop_compact_host_f32")
+    _launch("ptt_crop_compact_host_f32", device, ctypes.c_void_p(jobs_np.ctypes.data), int(n_jobs), timed='ptt_crop_compact_f32')
 
 
 def crop_compact_pinned(jobs_pinned, n_jobs, device):
     """ptt_crop_compact_f32 reading its job table straight from PINNED host memory (device-visible under unified addressing):
     the launch can then sit inside a hipGraph whose table the host rewrites between replays — no upload, no per-frame launch."""
-    with torch.cuda.device(device), _timed('ptt_crop_compact_f32'):
-        _lib.check(_lib.lib().ptt_crop_compact_f32(ctypes.c_void_p(jobs_pinned.data_ptr()), int(n_jobs), _stream()), "ptt_crop_compact_f32")
+    _launch("ptt_crop_compact_f32", device, ctypes.c_void_p(jobs_pinned.data_ptr()), int(n_jobs), timed='ptt_crop_compact_f32')
 
 
 def crop_regularize_pinned(crop_jobs_pinned, reg_jobs_dev, n_jobs, draws):
     """ptt_crop_regularize_f32: crop job w then resampling job w per workgroup, the crop table read from pinned host memory."""
-    with torch.cuda.device(reg_jobs_dev.device), _timed('ptt_crop_compact_f32'):
-        _lib.check(_lib.lib().ptt_crop_regularize_f32(ctypes.c_void_p(crop_jobs_pinned.data_ptr()), _ptr(reg_jobs_dev), int(n_jobs),
-                                                      _ptr(draws), draws.numel(), _stream()), "ptt_crop_regularize_f32")
+    _launch("ptt_crop_regularize_f32", reg_jobs_dev.device, ctypes.c_void_p(crop_jobs_pinned.data_ptr()), _ptr(reg_jobs_dev), int(n_jobs),
+            _ptr(draws), draws.numel(), timed='ptt_crop_compact_f32')
 
 
 def regularize(jobs_dev, n_jobs, draws):
     """ptt_regularize_f32 over a device-resident table of ptt_regularize_job records."""
-    with torch.cuda.device(jobs_dev.device), _timed('ptt_regularize_f32'):
-        _lib.check(_lib.lib().ptt_regularize_f32(_ptr(jobs_dev), int(n_jobs), _ptr(draws), draws.numel(), _stream()),
-                   "ptt_regularize_f32")
+    _launch("ptt_regularize_f32", jobs_dev.device, _ptr(jobs_dev), int(n_jobs), _ptr(draws), draws.numel(), timed='ptt_regularize_f32')
 
 
 def select_box(pred_box_data, out=None, idx_out=None):
@@ -790,9 +768,7 @@ def select_box(pred_box_data, out=None, idx_out=None):
         raise RuntimeError("pred_box_data must be (B,P,5)")
     if out is None:
         out = torch.empty((B, 5), dtype=torch.float32, device=pred_box_data.device)
-    with torch.cuda.device(pred_box_data.device):
-        _lib.check(_lib.lib().ptt_select_box_f32(_ptr(pred_box_data), B, P, _ptr(out), _ptr(idx_out), _stream()),
-                   "ptt_select_box_f32")
+    _launch("ptt_select_box_f32", pred_box_data.device, _ptr(pred_box_data), B, P, _ptr(out), _ptr(idx_out))
     return out
 
 
@@ -841,19 +817,14 @@ def bn_stats(x, eps, bn=None):
     _rows(x, "x")
     R, C = x.shape
     mean, var, invstd = (torch.empty((C,), dtype=torch.float32, device=x.device) for _ in range(3))
-    nb = _lib.lib().ptt_bn_stats_workspace(R, C)
-    ws = _ws(nb, x.device)
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", x.device, R, C)
     if bn is not None:
         tail, a, b = _bn_tail(bn, C, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ptt_bn_stats_train_f32(_ptr(x), R, C, x.stride(0), float(eps), _ptr(mean), _ptr(var), _ptr(invstd),
-                                                         _ptr(ws), ws.numel() * 8, ctypes.byref(tail), _stream()),
-                       "ptt_bn_stats_train_f32")
+        _launch("ptt_bn_stats_train_f32", x.device, _ptr(x), R, C, x.stride(0), float(eps), _ptr(mean), _ptr(var), _ptr(invstd), *ws_arg,
+                ctypes.byref(tail))
         _bn_tail_done(bn)
         return mean, var, invstd, a, b
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_bn_stats_f32(_ptr(x), R, C, x.stride(0), float(eps), _ptr(mean), _ptr(var), _ptr(invstd),
-                                               _ptr(ws), ws.numel() * 8, _stream()), "ptt_bn_stats_f32")
+    _launch("ptt_bn_stats_f32", x.device, _ptr(x), R, C, x.stride(0), float(eps), _ptr(mean), _ptr(var), _ptr(invstd), *ws_arg)
     return mean, var, invstd
 
 
@@ -863,9 +834,8 @@ def bn_apply(z, mean, invstd, gamma, beta, relu=True, out=None):
     R, C = z.shape
     if out is None:
         out = torch.empty((R, C), dtype=torch.float32, device=z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_apply_f32(_ptr(z), z.stride(0), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), R, C,
-                                               int(bool(relu)), _ptr(out), out.stride(0), _stream()), "ptt_bn_apply_f32")
+    _launch("ptt_bn_apply_f32", z.device, _ptr(z), z.stride(0), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), R, C, int(bool(relu)), _ptr(out),
+            out.stride(0))
     return out
 
 
@@ -880,12 +850,9 @@ def bn_bwd(g, act, z, mean, invstd, gamma, out=None, act_scale=None, act_shift=N
         out = torch.empty((R, C), dtype=torch.float32, device=z.device)
     dgamma = torch.empty((C,), dtype=torch.float32, device=z.device)
     dbeta = torch.empty((C,), dtype=torch.float32, device=z.device)
-    ws = _ws(_lib.lib().ptt_bn_stats_workspace(R, C), z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_f32(_ptr(g), g.stride(0), _ptr(act), act.stride(0) if act is not None else 0, _ptr(z),
-                                             z.stride(0), _ptr(mean), _ptr(invstd), _ptr(gamma), R, C, 1, _ptr(out),
-                                             out.stride(0), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 8,
-                                             _ptr(act_scale), _ptr(act_shift), _stream()), "ptt_bn_bwd_f32")
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", z.device, R, C)
+    _launch("ptt_bn_bwd_f32", z.device, _ptr(g), g.stride(0), _ptr(act), act.stride(0) if act is not None else 0, _ptr(z), z.stride(0), _ptr(mean),
+            _ptr(invstd), _ptr(gamma), R, C, 1, _ptr(out), out.stride(0), _ptr(dgamma), _ptr(dbeta), *ws_arg, _ptr(act_scale), _ptr(act_shift))
     return out, dgamma, dbeta
 
 
@@ -895,10 +862,8 @@ def bn_sums(x):
     _rows(x, "x")
     R, C = x.shape
     sums = torch.empty((2 * C + 1,), dtype=torch.float64, device=x.device)
-    ws = _ws(_lib.lib().ptt_bn_stats_workspace(R, C), x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_bn_sums_f64(_ptr(x), R, C, x.stride(0), _ptr(sums), _ptr(ws), ws.numel() * 8, _stream()),
-                   "ptt_bn_sums_f64")
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", x.device, R, C)
+    _launch("ptt_bn_sums_f64", x.device, _ptr(x), R, C, x.stride(0), _ptr(sums), *ws_arg)
     return sums
 
 
@@ -907,9 +872,7 @@ def bn_finish(sums, eps):
     the device — ptt_bn_finish_f64."""
     C = (sums.numel() - 1) // 2
     mean, var, invstd = (torch.empty((C,), dtype=torch.float32, device=sums.device) for _ in range(3))
-    with torch.cuda.device(sums.device):
-        _lib.check(_lib.lib().ptt_bn_finish_f64(_ptr(sums), C, float(eps), _ptr(mean), _ptr(var), _ptr(invstd), _stream()),
-                   "ptt_bn_finish_f64")
+    _launch("ptt_bn_finish_f64", sums.device, _ptr(sums), C, float(eps), _ptr(mean), _ptr(var), _ptr(invstd))
     return mean, var, invstd
 
 
@@ -918,12 +881,9 @@ def bn_bwd_sums(g, act, z, mean, invstd, act_scale=None, act_shift=None):
     _rows(g, "g"); _rows(z, "z")
     R, C = z.shape
     sums = torch.empty((2, C), dtype=torch.float64, device=z.device)
-    ws = _ws(_lib.lib().ptt_bn_stats_workspace(R, C), z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_sums_f64(_ptr(g), g.stride(0), _ptr(act), act.stride(0) if act is not None else 0, _ptr(z),
-                                                  z.stride(0), _ptr(mean), _ptr(invstd), R, C, _ptr(sums), _ptr(ws),
-                                                  ws.numel() * 8, _ptr(act_scale), _ptr(act_shift), _stream()),
-                   "ptt_bn_bwd_sums_f64")
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", z.device, R, C)
+    _launch("ptt_bn_bwd_sums_f64", z.device, _ptr(g), g.stride(0), _ptr(act), act.stride(0) if act is not None else 0, _ptr(z), z.stride(0),
+            _ptr(mean), _ptr(invstd), R, C, _ptr(sums), *ws_arg, _ptr(act_scale), _ptr(act_shift))
     return sums
 
 
@@ -934,11 +894,9 @@ def bn_bwd_apply(g, act, z, mean, invstd, gamma, sum_dy, sum_dy_xhat, count, out
     R, C = z.shape
     if out is None:
         out = torch.empty((R, C), dtype=torch.float32, device=z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_apply_f32(_ptr(g), g.stride(0), _ptr(act), act.stride(0) if act is not None else 0, _ptr(z),
-                                                   z.stride(0), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(sum_dy),
-                                                   _ptr(sum_dy_xhat), _ptr(count), R, C, _ptr(out), out.stride(0),
-                                                   _ptr(act_scale), _ptr(act_shift), _stream()), "ptt_bn_bwd_apply_f32")
+    _launch("ptt_bn_bwd_apply_f32", z.device, _ptr(g), g.stride(0), _ptr(act), act.stride(0) if act is not None else 0, _ptr(z), z.stride(0),
+            _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(sum_dy), _ptr(sum_dy_xhat), _ptr(count), R, C, _ptr(out), out.stride(0), _ptr(act_scale),
+            _ptr(act_shift))
     return out
 
 
@@ -946,11 +904,8 @@ def bn_update_running(bn, mean, var, count):
     """nn.BatchNorm's training-mode bookkeeping for module `bn` from the batch statistics, one launch
     (ptt_bn_update_running_f32); count: float64 (1,) device tensor = rows the statistics were taken over."""
     tracked = bn.num_batches_tracked
-    with torch.cuda.device(mean.device):
-        _lib.check(_lib.lib().ptt_bn_update_running_f32(_ptr(mean), _ptr(var), _ptr(count), float(bn.momentum), mean.numel(),
-                                                        _ptr(bn.running_mean), _ptr(bn.running_var),
-                                                        _ptr(tracked) if tracked is not None else None, _stream()),
-                   "ptt_bn_update_running_f32")
+    _launch("ptt_bn_update_running_f32", mean.device, _ptr(mean), _ptr(var), _ptr(count), float(bn.momentum), mean.numel(), _ptr(bn.running_mean),
+            _ptr(bn.running_var), _ptr(tracked) if tracked is not None else None)
     for t in (bn.running_mean, bn.running_var, tracked):          # the eval-mode parameter caches key on tensor versions
         if t is not None:
             torch.autograd.graph.increment_version(t)
@@ -962,14 +917,12 @@ def xcorr_z0(P, cos_t, w_sim, want_stats=False):
     B, n1, C = P.shape
     n2 = cos_t.shape[1]
     z0 = torch.empty((B * n2 * n1, C), dtype=torch.float32, device=P.device)
-    chunks = _lib.lib().ptt_xcorr_z0_stat_chunks(B, n2, n1, C) if want_stats else 0
-    with torch.cuda.device(P.device):
-        if chunks:
-            part = torch.empty((chunks, 2, C), dtype=torch.float64, device=P.device)
-            _lib.check(_lib.lib().ptt_xcorr_z0_stats_f32(_ptr(P), _ptr(cos_t), _ptr(w_sim), B, n2, n1, C, _ptr(z0), _ptr(part), part.numel(),
-                                                         _stream()), "ptt_xcorr_z0_stats_f32")
-            return z0, part
-        _lib.check(_lib.lib().ptt_xcorr_z0_f32(_ptr(P), _ptr(cos_t), _ptr(w_sim), B, n2, n1, C, _ptr(z0), _stream()), "ptt_xcorr_z0_f32")
+    chunks = _host("ptt_xcorr_z0_stat_chunks", B, n2, n1, C) if want_stats else 0
+    if chunks:
+        part = torch.empty((chunks, 2, C), dtype=torch.float64, device=P.device)
+        _launch("ptt_xcorr_z0_stats_f32", P.device, _ptr(P), _ptr(cos_t), _ptr(w_sim), B, n2, n1, C, _ptr(z0), _ptr(part), part.numel())
+        return z0, part
+    _launch("ptt_xcorr_z0_f32", P.device, _ptr(P), _ptr(cos_t), _ptr(w_sim), B, n2, n1, C, _ptr(z0))
     return (z0, None) if want_stats else z0
 
 
@@ -979,10 +932,8 @@ def xcorr_z0_bwd(dz0, cos_t, w_sim, B, n2, n1):
     dP = torch.empty((B, n1, C), dtype=torch.float32, device=dz0.device)
     dcos = torch.empty((B, n2, n1), dtype=torch.float32, device=dz0.device)
     dw = torch.empty((C,), dtype=torch.float32, device=dz0.device)
-    ws = _ws(_lib.lib().ptt_xcorr_z0_bwd_workspace(B, n1, C), dz0.device)
-    with torch.cuda.device(dz0.device):
-        _lib.check(_lib.lib().ptt_xcorr_z0_bwd_f32(_ptr(dz0), _ptr(cos_t), _ptr(w_sim), B, n2, n1, C, _ptr(dP), _ptr(dcos), _ptr(dw),
-                                                   _ptr(ws), ws.numel() * 8, _stream()), "ptt_xcorr_z0_bwd_f32")
+    ws, ws_arg = _workspace("ptt_xcorr_z0_bwd_workspace", dz0.device, B, n1, C)
+    _launch("ptt_xcorr_z0_bwd_f32", dz0.device, _ptr(dz0), _ptr(cos_t), _ptr(w_sim), B, n2, n1, C, _ptr(dP), _ptr(dcos), _ptr(dw), *ws_arg)
     return dP, dcos, dw
 
 
@@ -996,11 +947,9 @@ def xcorr_z0_bnbwd(part, g, P, cos_t, w_sim, mean, invstd, gamma, act_scale, act
     dP = torch.empty((B, n1, C), dtype=torch.float32, device=dev)
     dcos = torch.empty((B, n2, n1), dtype=torch.float32, device=dev)
     dw, dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(3))
-    ws = _ws(_lib.lib().ptt_xcorr_z0_bwd_workspace(B, n1, C), dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ptt_xcorr_z0_bnbwd_f32(_ptr(part), part.shape[0], _ptr(g), _ptr(P), _ptr(cos_t), _ptr(w_sim), _ptr(mean), _ptr(invstd),
-                                                     _ptr(gamma), _ptr(act_scale), _ptr(act_shift), B, n2, n1, C, _ptr(dP), _ptr(dcos), _ptr(dw),
-                                                     _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 8, _stream()), "ptt_xcorr_z0_bnbwd_f32")
+    ws, ws_arg = _workspace("ptt_xcorr_z0_bwd_workspace", dev, B, n1, C)
+    _launch("ptt_xcorr_z0_bnbwd_f32", dev, _ptr(part), part.shape[0], _ptr(g), _ptr(P), _ptr(cos_t), _ptr(w_sim), _ptr(mean), _ptr(invstd),
+            _ptr(gamma), _ptr(act_scale), _ptr(act_shift), B, n2, n1, C, _ptr(dP), _ptr(dcos), _ptr(dw), _ptr(dgamma), _ptr(dbeta), *ws_arg)
     return dP, dcos, dw, dgamma, dbeta
 
 
@@ -1013,12 +962,9 @@ def bn_bwd_pooled(dpooled, arg, ns, z, mean, invstd, gamma, act_scale, act_shift
         out = torch.empty((R, C), dtype=torch.float32, device=z.device)
     dgamma = torch.empty((C,), dtype=torch.float32, device=z.device)
     dbeta = torch.empty((C,), dtype=torch.float32, device=z.device)
-    ws = _ws(_lib.lib().ptt_bn_stats_workspace(R, C), z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_pooled_f32(_ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0), _ptr(mean),
-                                                    _ptr(invstd), _ptr(gamma), R, C, _ptr(out), out.stride(0), _ptr(dgamma), _ptr(dbeta),
-                                                    _ptr(ws), ws.numel() * 8, _ptr(act_scale), _ptr(act_shift), _stream()),
-                   "ptt_bn_bwd_pooled_f32")
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", z.device, R, C)
+    _launch("ptt_bn_bwd_pooled_f32", z.device, _ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0), _ptr(mean), _ptr(invstd),
+            _ptr(gamma), R, C, _ptr(out), out.stride(0), _ptr(dgamma), _ptr(dbeta), *ws_arg, _ptr(act_scale), _ptr(act_shift))
     return out, dgamma, dbeta
 
 
@@ -1027,11 +973,9 @@ def bn_bwd_pooled_sums(dpooled, arg, ns, z, mean, invstd, act_scale, act_shift):
     _rows(dpooled, "dpooled"); _rows(z, "z")
     R, C = z.shape
     sums = torch.empty((2, C), dtype=torch.float64, device=z.device)
-    ws = _ws(_lib.lib().ptt_bn_stats_workspace(R, C), z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_pooled_sums_f64(_ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0),
-                                                         _ptr(mean), _ptr(invstd), R, C, _ptr(sums), _ptr(ws), ws.numel() * 8,
-                                                         _ptr(act_scale), _ptr(act_shift), _stream()), "ptt_bn_bwd_pooled_sums_f64")
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", z.device, R, C)
+    _launch("ptt_bn_bwd_pooled_sums_f64", z.device, _ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0), _ptr(mean),
+            _ptr(invstd), R, C, _ptr(sums), *ws_arg, _ptr(act_scale), _ptr(act_shift))
     return sums
 
 
@@ -1041,11 +985,8 @@ def bn_bwd_pooled_apply(dpooled, arg, ns, z, mean, invstd, gamma, sum_dy, sum_dy
     R, C = z.shape
     if out is None:
         out = torch.empty((R, C), dtype=torch.float32, device=z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_pooled_apply_f32(_ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0),
-                                                          _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(sum_dy), _ptr(sum_dy_xhat),
-                                                          _ptr(count), R, C, _ptr(out), out.stride(0), _ptr(act_scale),
-                                                          _ptr(act_shift), _stream()), "ptt_bn_bwd_pooled_apply_f32")
+    _launch("ptt_bn_bwd_pooled_apply_f32", z.device, _ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0), _ptr(mean),
+            _ptr(invstd), _ptr(gamma), _ptr(sum_dy), _ptr(sum_dy_xhat), _ptr(count), R, C, _ptr(out), out.stride(0), _ptr(act_scale), _ptr(act_shift))
     return out
 
 
@@ -1057,9 +998,7 @@ def pool_rows(x, ns, act_scale=None, act_shift=None):
     G = R // int(ns)
     out = torch.empty((G, C), dtype=torch.float32, device=x.device)
     arg = torch.empty((G, C), dtype=torch.int32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_pool_rows_f32(_ptr(x), x.stride(0), G, int(ns), C, _ptr(out), C, _ptr(arg), _ptr(act_scale),
-                                                _ptr(act_shift), _stream()), "ptt_pool_rows_f32")
+    _launch("ptt_pool_rows_f32", x.device, _ptr(x), x.stride(0), G, int(ns), C, _ptr(out), C, _ptr(arg), _ptr(act_scale), _ptr(act_shift))
     return out, arg
 
 
@@ -1067,9 +1006,7 @@ def pool_rows_bwd(dout, arg, ns):
     _rows(dout, "dout")
     G, C = dout.shape
     dx = torch.empty((G * int(ns), C), dtype=torch.float32, device=dout.device)
-    with torch.cuda.device(dout.device):
-        _lib.check(_lib.lib().ptt_pool_rows_bwd_f32(_ptr(dout), dout.stride(0), _ptr(arg), G, int(ns), C, _ptr(dx), C, _stream()),
-                   "ptt_pool_rows_bwd_f32")
+    _launch("ptt_pool_rows_bwd_f32", dout.device, _ptr(dout), dout.stride(0), _ptr(arg), G, int(ns), C, _ptr(dx), C)
     return dx
 
 
@@ -1078,9 +1015,8 @@ def linear_act_in(x, in_scale, in_shift, wpacked, cout):
     _rows(x, "x")
     rows, K = x.shape
     out = torch.empty((rows, int(cout)), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
-        _lib.check(_lib.lib().ptt_linear_act_in_f32(_ptr(x), rows, K, x.stride(0), _ptr(in_scale), _ptr(in_shift), _ptr(wpacked),
-                                                    int(cout), _ptr(out), int(cout), _stream()), "ptt_linear_act_in_f32")
+    _launch("ptt_linear_act_in_f32", x.device, _ptr(x), rows, K, x.stride(0), _ptr(in_scale), _ptr(in_shift), _ptr(wpacked), int(cout), _ptr(out),
+            int(cout), timed='ptt_linear_f32')
     return out
 
 
@@ -1090,7 +1026,7 @@ def rows_gemm_supported(rows, K, N, ldx=None, ldo=None, x=None):
     first falls back to the linear kernel instead of meeting PTT_EINVAL."""
     if x is not None and x.data_ptr() % 16:
         return False
-    return bool(_lib.lib().ptt_rows_gemm_supported(int(rows), int(K), int(N), int(ldx if ldx is not None else K),
+    return bool(_host("ptt_rows_gemm_supported", int(rows), int(K), int(N), int(ldx if ldx is not None else K),
                                                    int(ldo if ldo is not None else N)))
 
 
@@ -1106,23 +1042,21 @@ def rows_gemm(x, wpacked, cout, in_scale=None, in_shift=None, bias=None, relu=Fa
         out = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
     stats = None
     if want_stats:
-        chunks = _lib.lib().ptt_rows_gemm_stat_chunks(rows, K, cout)
+        chunks = _host("ptt_rows_gemm_stat_chunks", rows, K, cout)
         stats = torch.empty((max(1, chunks), 2, cout), dtype=torch.float64, device=x.device)
     r2 = None
     if residual is not None:
         r2 = _rows(residual, "residual")
-    with torch.cuda.device(x.device), _timed('ptt_rows_gemm_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_f32(_ptr(x), rows, K, x.stride(0), _ptr(in_scale), _ptr(in_shift), _ptr(wpacked), cout,
-                                                _ptr(bias), 1 if relu else 0, _ptr(r2), r2.stride(0) if r2 is not None else cout,
-                                                _ptr(out), out.stride(0), _ptr(stats), stats.numel() if stats is not None else 0,
-                                                _stream()), "ptt_rows_gemm_f32")
+    _launch("ptt_rows_gemm_f32", x.device, _ptr(x), rows, K, x.stride(0), _ptr(in_scale), _ptr(in_shift), _ptr(wpacked), cout, _ptr(bias),
+            1 if relu else 0, _ptr(r2), r2.stride(0) if r2 is not None else cout, _ptr(out), out.stride(0), _ptr(stats),
+            stats.numel() if stats is not None else 0, timed='ptt_rows_gemm_f32')
     return (out, stats) if want_stats else out
 
 
 def rows_gemm_pool_supported(rows, K, N, ldx, ns, x=None):
     if x is not None and x.data_ptr() % 16:
         return False
-    return bool(_lib.lib().ptt_rows_gemm_pool_supported(int(rows), int(K), int(N), int(ldx), int(ns)))
+    return bool(_host("ptt_rows_gemm_pool_supported", int(rows), int(K), int(N), int(ldx), int(ns)))
 
 
 def rows_gemm_pool(x, wpacked, cout, in_scale, in_shift, ns):
@@ -1134,16 +1068,14 @@ def rows_gemm_pool(x, wpacked, cout, in_scale, in_shift, ns):
     cout, ns = int(cout), int(ns)
     G = rows // ns
     out = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-    chunks = _lib.lib().ptt_rows_gemm_stat_chunks(rows, K, cout)
+    chunks = _host("ptt_rows_gemm_stat_chunks", rows, K, cout)
     stats = torch.empty((max(1, chunks), 2, cout), dtype=torch.float64, device=x.device)
     pmax = torch.empty((G, cout), dtype=torch.float32, device=x.device)
     pmin = torch.empty((G, cout), dtype=torch.float32, device=x.device)
     amax = torch.empty((G, cout), dtype=torch.int32, device=x.device)
     amin = torch.empty((G, cout), dtype=torch.int32, device=x.device)
-    with torch.cuda.device(x.device), _timed('ptt_rows_gemm_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_pool_f32(_ptr(x), rows, K, x.stride(0), _ptr(in_scale), _ptr(in_shift), _ptr(wpacked), cout,
-                                                     _ptr(out), cout, _ptr(stats), stats.numel(), ns, _ptr(pmax), _ptr(pmin), _ptr(amax),
-                                                     _ptr(amin), _stream()), "ptt_rows_gemm_pool_f32")
+    _launch("ptt_rows_gemm_pool_f32", x.device, _ptr(x), rows, K, x.stride(0), _ptr(in_scale), _ptr(in_shift), _ptr(wpacked), cout, _ptr(out), cout,
+            _ptr(stats), stats.numel(), ns, _ptr(pmax), _ptr(pmin), _ptr(amax), _ptr(amin), timed='ptt_rows_gemm_f32')
     return out, stats, (pmax, pmin, amax, amin)
 
 
@@ -1153,9 +1085,8 @@ def pool_select(extrema, act_scale, act_shift):
     G, C = pmax.shape
     out = torch.empty((G, C), dtype=torch.float32, device=pmax.device)
     arg = torch.empty((G, C), dtype=torch.int32, device=pmax.device)
-    with torch.cuda.device(pmax.device):
-        _lib.check(_lib.lib().ptt_pool_select_f32(_ptr(pmax), _ptr(pmin), _ptr(amax), _ptr(amin), _ptr(act_scale), _ptr(act_shift), G, C,
-                                                  _ptr(out), _ptr(arg), _stream()), "ptt_pool_select_f32")
+    _launch("ptt_pool_select_f32", pmax.device, _ptr(pmax), _ptr(pmin), _ptr(amax), _ptr(amin), _ptr(act_scale), _ptr(act_shift), G, C, _ptr(out),
+            _ptr(arg))
     return out, arg
 
 
@@ -1169,12 +1100,10 @@ def rows_gemm_masked(x, wpacked, cout, mask, want_colsum=False):
     out = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
     stats = None
     if want_colsum:
-        chunks = _lib.lib().ptt_rows_gemm_stat_chunks(rows, K, cout)
+        chunks = _host("ptt_rows_gemm_stat_chunks", rows, K, cout)
         stats = torch.empty((max(1, chunks), 2, cout), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device), _timed('ptt_rows_gemm_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_masked_f32(_ptr(x), rows, K, x.stride(0), _ptr(wpacked), cout, _ptr(mask), mask.stride(0),
-                                                       _ptr(out), cout, _ptr(stats), stats.numel() if stats is not None else 0,
-                                                       _stream()), "ptt_rows_gemm_masked_f32")
+    _launch("ptt_rows_gemm_masked_f32", x.device, _ptr(x), rows, K, x.stride(0), _ptr(wpacked), cout, _ptr(mask), mask.stride(0), _ptr(out), cout,
+            _ptr(stats), stats.numel() if stats is not None else 0, timed='ptt_rows_gemm_f32')
     if want_colsum:
         return out, bn_sums_partials(stats, rows)[:cout].float()
     return out
@@ -1187,12 +1116,10 @@ def rows_gemm_bnbwd(x, wpacked, cout, z, mean, invstd, act_scale, act_shift):
     rows, K = x.shape
     cout = int(cout)
     out = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-    chunks = _lib.lib().ptt_rows_gemm_stat_chunks(rows, K, cout)
+    chunks = _host("ptt_rows_gemm_stat_chunks", rows, K, cout)
     part = torch.empty((max(1, chunks), 2, cout), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device), _timed('ptt_rows_gemm_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_bnbwd_f32(_ptr(x), rows, K, x.stride(0), _ptr(wpacked), cout, _ptr(z), z.stride(0), _ptr(mean),
-                                                      _ptr(invstd), _ptr(act_scale), _ptr(act_shift), _ptr(out), cout, _ptr(part),
-                                                      part.numel(), _stream()), "ptt_rows_gemm_bnbwd_f32")
+    _launch("ptt_rows_gemm_bnbwd_f32", x.device, _ptr(x), rows, K, x.stride(0), _ptr(wpacked), cout, _ptr(z), z.stride(0), _ptr(mean), _ptr(invstd),
+            _ptr(act_scale), _ptr(act_shift), _ptr(out), cout, _ptr(part), part.numel(), timed='ptt_rows_gemm_f32')
     return out, part
 
 
@@ -1203,11 +1130,8 @@ def bn_bwd_from_partials(part, g, z, mean, invstd, gamma, act_scale, act_shift, 
         out = torch.empty((R, C), dtype=torch.float32, device=z.device)
     dgamma = torch.empty((C,), dtype=torch.float32, device=z.device)
     dbeta = torch.empty((C,), dtype=torch.float32, device=z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_from_partials_f32(_ptr(part), part.shape[0], _ptr(g), g.stride(0), _ptr(z), z.stride(0), _ptr(mean),
-                                                           _ptr(invstd), _ptr(gamma), R, C, _ptr(out), out.stride(0), _ptr(dgamma),
-                                                           _ptr(dbeta), _ptr(act_scale), _ptr(act_shift), _stream()),
-                   "ptt_bn_bwd_from_partials_f32")
+    _launch("ptt_bn_bwd_from_partials_f32", z.device, _ptr(part), part.shape[0], _ptr(g), g.stride(0), _ptr(z), z.stride(0), _ptr(mean), _ptr(invstd),
+            _ptr(gamma), R, C, _ptr(out), out.stride(0), _ptr(dgamma), _ptr(dbeta), _ptr(act_scale), _ptr(act_shift))
     return out, dgamma, dbeta
 
 
@@ -1219,9 +1143,8 @@ def bn_bwd_consts(part, mean, invstd, gamma, rows):
     # dgamma / dbeta become .grad of their parameters: tensors of their own, not rows of the constants' buffer
     dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=part.device) for _ in range(2))
     out = torch.empty((3, C), dtype=torch.float32, device=part.device)
-    with torch.cuda.device(part.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_consts_f32(_ptr(part), chunks, _ptr(mean), _ptr(invstd), _ptr(gamma), int(rows), C, _ptr(dgamma),
-                                                    _ptr(dbeta), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "ptt_bn_bwd_consts_f32")
+    _launch("ptt_bn_bwd_consts_f32", part.device, _ptr(part), chunks, _ptr(mean), _ptr(invstd), _ptr(gamma), int(rows), C, _ptr(dgamma), _ptr(dbeta),
+            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]))
     return dgamma, dbeta, (out[0], out[1], out[2])
 
 
@@ -1231,18 +1154,16 @@ def bn_bwd_pooled_consts(dpooled, arg, ns, z, mean, invstd, gamma, act_scale, ac
     R, C = z.shape
     dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=z.device) for _ in range(2))
     out = torch.empty((3, C), dtype=torch.float32, device=z.device)
-    ws = _ws(_lib.lib().ptt_bn_stats_workspace(R, C), z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_pooled_consts_f32(_ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0), _ptr(mean),
-                                                           _ptr(invstd), _ptr(gamma), R, C, _ptr(dgamma), _ptr(dbeta), _ptr(out[0]), _ptr(out[1]),
-                                                           _ptr(out[2]), _ptr(ws), ws.numel() * 8, _ptr(act_scale), _ptr(act_shift), _stream()),
-                   "ptt_bn_bwd_pooled_consts_f32")
+    ws, ws_arg = _workspace("ptt_bn_stats_workspace", z.device, R, C)
+    _launch("ptt_bn_bwd_pooled_consts_f32", z.device, _ptr(dpooled), dpooled.stride(0), _ptr(arg), int(ns), _ptr(z), z.stride(0), _ptr(mean),
+            _ptr(invstd), _ptr(gamma), R, C, _ptr(dgamma), _ptr(dbeta), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), *ws_arg, _ptr(act_scale),
+            _ptr(act_shift))
     return dgamma, dbeta, (out[0], out[1], out[2])
 
 
 def rows_gemm_bnbwd_fused_supported(rows, K, cout, ns, *tensors):
     """ptt_rows_gemm_bnbwd_fused_f32 takes the shape and the layouts: contiguous 16-byte aligned rows (row stride == K)."""
-    if not _lib.lib().ptt_rows_gemm_bnbwd_fused_supported(int(rows), int(K), int(cout), int(ns)):
+    if not _host("ptt_rows_gemm_bnbwd_fused_supported", int(rows), int(K), int(cout), int(ns)):
         return False
     return all(t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
                for t in tensors if t is not None)
@@ -1258,16 +1179,14 @@ def rows_gemm_bnbwd_fused(g, arg, ns, z, consts, mean, act_a, act_b, wpacked, co
     dev = z.device
     out = torch.empty((rows, cout), dtype=torch.float32, device=dev)
     dz = torch.empty((rows, K), dtype=torch.float32, device=dev) if want_dz else None
-    chunks = _lib.lib().ptt_rows_gemm_stat_chunks(rows, K, cout)
+    chunks = _host("ptt_rows_gemm_stat_chunks", rows, K, cout)
     part = torch.empty((max(1, chunks), 2, cout), dtype=torch.float64, device=dev)
     d = _lib.BnBwdInput(g=g.data_ptr(), ldg=g.stride(0), arg=arg.data_ptr() if arg is not None else None, ns=int(ns), z=z.data_ptr(),
                         ldz=z.stride(0), k1=consts[0].data_ptr(), c0=consts[1].data_ptr(), c1=consts[2].data_ptr(), mean=mean.data_ptr(),
                         act_a=act_a.data_ptr(), act_b=act_b.data_ptr(), dz_out=dz.data_ptr() if dz is not None else None,
                         ldd=dz.stride(0) if dz is not None else 0)
-    with torch.cuda.device(dev), _timed('ptt_rows_gemm_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_bnbwd_fused_f32(ctypes.byref(d), rows, K, _ptr(wpacked), cout, _ptr(zp), zp.stride(0), _ptr(mp),
-                                                            _ptr(ip), _ptr(ap), _ptr(bp), _ptr(out), cout, _ptr(part), part.numel(), _stream()),
-                   "ptt_rows_gemm_bnbwd_fused_f32")
+    _launch("ptt_rows_gemm_bnbwd_fused_f32", dev, ctypes.byref(d), rows, K, _ptr(wpacked), cout, _ptr(zp), zp.stride(0), _ptr(mp), _ptr(ip), _ptr(ap),
+            _ptr(bp), _ptr(out), cout, _ptr(part), part.numel(), timed='ptt_rows_gemm_f32')
     return out, part, dz
 
 
@@ -1275,8 +1194,7 @@ def bn_bwd_sums_from_partials(part):
     """The (2, C) float64 sums of bn_bwd_sums from rows_gemm_bnbwd's partials (SyncBatchNorm: all-reduce them, then bn_bwd_apply)."""
     chunks, _, C = part.shape
     sums = torch.empty((2, C), dtype=torch.float64, device=part.device)
-    with torch.cuda.device(part.device):
-        _lib.check(_lib.lib().ptt_bn_bwd_sums_partials_f64(_ptr(part), chunks, C, _ptr(sums), _stream()), "ptt_bn_bwd_sums_partials_f64")
+    _launch("ptt_bn_bwd_sums_partials_f64", part.device, _ptr(part), chunks, C, _ptr(sums))
     return sums
 
 
@@ -1287,15 +1205,11 @@ def bn_finish_partials(partials, rows, eps, bn=None):
     mean, var, invstd = (torch.empty((C,), dtype=torch.float32, device=partials.device) for _ in range(3))
     if bn is not None:
         tail, a, b = _bn_tail(bn, C, partials.device)
-        with torch.cuda.device(partials.device):
-            _lib.check(_lib.lib().ptt_bn_finish_partials_train_f32(_ptr(partials), chunks, C, int(rows), float(eps), _ptr(mean),
-                                                                   _ptr(var), _ptr(invstd), ctypes.byref(tail), _stream()),
-                       "ptt_bn_finish_partials_train_f32")
+        _launch("ptt_bn_finish_partials_train_f32", partials.device, _ptr(partials), chunks, C, int(rows), float(eps), _ptr(mean), _ptr(var),
+                _ptr(invstd), ctypes.byref(tail))
         _bn_tail_done(bn)
         return mean, var, invstd, a, b
-    with torch.cuda.device(partials.device):
-        _lib.check(_lib.lib().ptt_bn_finish_partials_f32(_ptr(partials), chunks, C, int(rows), float(eps), _ptr(mean), _ptr(var),
-                                                         _ptr(invstd), _stream()), "ptt_bn_finish_partials_f32")
+    _launch("ptt_bn_finish_partials_f32", partials.device, _ptr(partials), chunks, C, int(rows), float(eps), _ptr(mean), _ptr(var), _ptr(invstd))
     return mean, var, invstd
 
 
@@ -1303,9 +1217,7 @@ def bn_sums_partials(partials, rows):
     """rows_gemm's partial sums -> the 2C + 1 float64 vector of bn_sums (sum, sum of squares, row count) for SyncBatchNorm."""
     chunks, _, C = partials.shape
     sums = torch.empty((2 * C + 1,), dtype=torch.float64, device=partials.device)
-    with torch.cuda.device(partials.device):
-        _lib.check(_lib.lib().ptt_bn_sums_partials_f64(_ptr(partials), chunks, C, int(rows), _ptr(sums), _stream()),
-                   "ptt_bn_sums_partials_f64")
+    _launch("ptt_bn_sums_partials_f64", partials.device, _ptr(partials), chunks, C, int(rows), _ptr(sums))
     return sums
 
 
@@ -1318,9 +1230,8 @@ def colsum(x, out=None):
         return x.sum(0) if out is None else out.zero_()
     if out is None:
         out = torch.empty((C,), dtype=torch.float32, device=x.device)
-    ws = _ws(_lib.lib().ptt_colsum_workspace(R, C), x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_colsum_f32(_ptr(x), R, C, x.stride(0), _ptr(out), _ptr(ws), ws.numel() * 8, _stream()), "ptt_colsum_f32")
+    ws, ws_arg = _workspace("ptt_colsum_workspace", x.device, R, C)
+    _launch("ptt_colsum_f32", x.device, _ptr(x), R, C, x.stride(0), _ptr(out), *ws_arg)
     return out
 
 
@@ -1337,19 +1248,11 @@ def linear_wgrad(dz, x, out=None, accumulate=False, x_scale=None, x_shift=None):
     # float4 rows (stride % 4, 16-byte aligned) and 32-bit element offsets (R * stride < 2^29)
     ok2 = (dz.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and dz.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
            and R * max(dz.stride(0), x.stride(0)) < (1 << 29))
-    nb2 = _lib.lib().ptt_linear_wgrad2_workspace(R, Cout, Cin) if ok2 else 0
-    if nb2 and WGRAD2:
-        ws = _ws(nb2, dz.device)
-        with torch.cuda.device(dz.device), _timed('ptt_linear_wgrad_f32'):
-            _lib.check(_lib.lib().ptt_linear_wgrad2_f32(_ptr(dz), dz.stride(0), _ptr(x), x.stride(0), R, Cout, Cin, _ptr(out),
-                                                        int(bool(accumulate)), _ptr(ws), ws.numel() * 8, _ptr(x_scale), _ptr(x_shift),
-                                                        _stream()), "ptt_linear_wgrad2_f32")
-        return out
-    ws = _ws(_lib.lib().ptt_linear_wgrad_workspace(R, Cout, Cin), dz.device)
-    with torch.cuda.device(dz.device), _timed('ptt_linear_wgrad_f32'):
-        _lib.check(_lib.lib().ptt_linear_wgrad_f32(_ptr(dz), dz.stride(0), _ptr(x), x.stride(0), R, Cout, Cin, _ptr(out),
-                                                   int(bool(accumulate)), _ptr(ws), ws.numel() * 8, _ptr(x_scale), _ptr(x_shift),
-                                                   _stream()), "ptt_linear_wgrad_f32")
+    nb2 = _host("ptt_linear_wgrad2_workspace", R, Cout, Cin) if ok2 else 0
+    two = bool(nb2 and WGRAD2)
+    ws = _ws(nb2 if two else _host("ptt_linear_wgrad_workspace", R, Cout, Cin), dz.device)
+    _launch("ptt_linear_wgrad2_f32" if two else "ptt_linear_wgrad_f32", dz.device, _ptr(dz), dz.stride(0), _ptr(x), x.stride(0), R, Cout, Cin,
+            _ptr(out), int(bool(accumulate)), _ptr(ws), ws.numel() * 8, _ptr(x_scale), _ptr(x_shift), timed='ptt_linear_wgrad_f32')
     return out
 
 
@@ -1361,14 +1264,12 @@ def linear_wgrad_partials(dz, x, x_scale=None, x_shift=None):
     Cin = x.shape[1]
     ok2 = (dz.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and dz.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
            and R * max(dz.stride(0), x.stride(0)) < (1 << 29))
-    nb2 = _lib.lib().ptt_linear_wgrad2_workspace(R, Cout, Cin) if ok2 else 0
+    nb2 = _host("ptt_linear_wgrad2_workspace", R, Cout, Cin) if ok2 else 0
     nch = ctypes.c_int(0)
     two = bool(nb2 and WGRAD2)
-    ws = _ws(nb2 if two else _lib.lib().ptt_linear_wgrad_workspace(R, Cout, Cin), dz.device)
-    fn = _lib.lib().ptt_linear_wgrad2_partials_f32 if two else _lib.lib().ptt_linear_wgrad_partials_f32
-    with torch.cuda.device(dz.device), _timed('ptt_linear_wgrad_f32'):
-        _lib.check(fn(_ptr(dz), dz.stride(0), _ptr(x), x.stride(0), R, Cout, Cin, _ptr(ws), ws.numel() * 8, _ptr(x_scale), _ptr(x_shift),
-                      ctypes.byref(nch), _stream()), "ptt_linear_wgrad_partials_f32")
+    ws = _ws(nb2 if two else _host("ptt_linear_wgrad_workspace", R, Cout, Cin), dz.device)
+    _launch("ptt_linear_wgrad2_partials_f32" if two else "ptt_linear_wgrad_partials_f32", dz.device, _ptr(dz), dz.stride(0), _ptr(x), x.stride(0),
+            R, Cout, Cin, _ptr(ws), ws.numel() * 8, _ptr(x_scale), _ptr(x_shift), ctypes.byref(nch), timed='ptt_linear_wgrad_f32')
     return ws, nch.value
 
 
@@ -1376,11 +1277,9 @@ def colsum_partials(x):
     """colsum without its finishing launch: -> (workspace holding [nchunks][C] float32 partial column sums, nchunks)."""
     _rows(x, "x")
     R, C = x.shape
-    ws = _ws(_lib.lib().ptt_colsum_workspace(R, C), x.device)
+    ws, ws_arg = _workspace("ptt_colsum_workspace", x.device, R, C)
     nch = ctypes.c_int(0)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_colsum_partials_f32(_ptr(x), R, C, x.stride(0), _ptr(ws), ws.numel() * 8, ctypes.byref(nch), _stream()),
-                   "ptt_colsum_partials_f32")
+    _launch("ptt_colsum_partials_f32", x.device, _ptr(x), R, C, x.stride(0), *ws_arg, ctypes.byref(nch))
     return ws, nch.value
 
 
@@ -1501,9 +1400,7 @@ class GradFinishPlan(object):
         if not capturing:
             self.table.copy_(self.host, non_blocking=True)
             self.uploaded.record()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ptt_grad_finish_f32(_ptr(self.segs), _ptr(table), _ptr(self.blocks), self.n_blocks, _ptr(flat), _stream()),
-                       "ptt_grad_finish_f32")
+        _launch("ptt_grad_finish_f32", self.device, _ptr(self.segs), _ptr(table), _ptr(self.blocks), self.n_blocks, _ptr(flat))
 
 
 # --------------------------------------------------------------------------- T-opt: dense attention as batched MFMA GEMMs
@@ -1512,11 +1409,10 @@ def pack_weight_strided(src, cout, k, stride_out, stride_k, batch, stride_batch)
     MFMA B-fragment buffers, (batch, ptt_packed_weight_elems(cout, k)) — ptt_pack_weight_strided_f32."""
     if not src.is_cuda or src.dtype != torch.float32:
         raise RuntimeError("src must be a float32 device tensor")
-    n = _lib.lib().ptt_packed_weight_elems(int(cout), int(k))
+    n = _host("ptt_packed_weight_elems", int(cout), int(k))
     out = torch.empty((int(batch), n), dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().ptt_pack_weight_strided_f32(_ptr(src), int(cout), int(k), int(stride_out), int(stride_k), int(batch),
-                                                          int(stride_batch), _ptr(out), _stream()), "ptt_pack_weight_strided_f32")
+    _launch("ptt_pack_weight_strided_f32", src.device, _ptr(src), int(cout), int(k), int(stride_out), int(stride_k), int(batch), int(stride_batch),
+            _ptr(out))
     return out
 
 
@@ -1533,8 +1429,7 @@ def pack_weights(table, n_jobs, arena):
     """Packs the n_jobs weights of a pack_jobs_table into `arena` (float32, 1-D) in one launch — ptt_pack_weights_f32."""
     if not arena.is_cuda or arena.dtype != torch.float32 or not arena.is_contiguous():
         raise RuntimeError("arena must be a contiguous float32 device tensor")
-    with torch.cuda.device(arena.device):
-        _lib.check(_lib.lib().ptt_pack_weights_f32(_ptr(table), int(n_jobs), _ptr(arena), _stream()), "ptt_pack_weights_f32")
+    _launch("ptt_pack_weights_f32", arena.device, _ptr(table), int(n_jobs), _ptr(arena))
     return arena
 
 
@@ -1548,11 +1443,9 @@ def linear_batched(x, wpacked, cout, residual=None):
     r = residual
     if r is not None and (r.dim() != 3 or r.stride(2) != 1):
         raise RuntimeError("residual must be (batch, rows, cout) with contiguous channels")
-    with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
-        _lib.check(_lib.lib().ptt_linear_batched_f32(
-            _ptr(x), rows, K, x.stride(1), x.stride(0), _ptr(wpacked), wpacked.stride(0), int(cout), None, None, 0,
-            _ptr(r), r.stride(1) if r is not None else int(cout), r.stride(0) if r is not None else 0,
-            _ptr(out), int(cout), rows * int(cout), Bt, _stream()), "ptt_linear_batched_f32")
+    _launch("ptt_linear_batched_f32", x.device, _ptr(x), rows, K, x.stride(1), x.stride(0), _ptr(wpacked), wpacked.stride(0), int(cout), None, None,
+            0, _ptr(r), r.stride(1) if r is not None else int(cout), r.stride(0) if r is not None else 0, _ptr(out), int(cout), rows * int(cout), Bt,
+            timed='ptt_linear_f32')
     return out
 
 
@@ -1560,8 +1453,7 @@ def softmax_rows_(x, scale):
     """In-place softmax(scale * x) along the last dim of a contiguous float32 device tensor."""
     _chk(x, "x", torch.float32)
     n = x.shape[-1]
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_softmax_rows_f32(_ptr(x), x.numel() // n, n, n, float(scale), _stream()), "ptt_softmax_rows_f32")
+    _launch("ptt_softmax_rows_f32", x.device, _ptr(x), x.numel() // n, n, n, float(scale))
     return x
 
 
@@ -1572,8 +1464,7 @@ def gather_rows(src, idx):
     B, N, C = src.shape
     E = idx.shape[1]
     out = torch.empty((B, E, C), dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().ptt_gather_rows_f32(_ptr(src), _ptr(idx), B, N, E, C, _ptr(out), _stream()), "ptt_gather_rows_f32")
+    _launch("ptt_gather_rows_f32", src.device, _ptr(src), _ptr(idx), B, N, E, C, _ptr(out))
     return out
 
 
@@ -1597,17 +1488,14 @@ def sa_z0_rows(xyz, new_xyz, idx, term, wx, radius, normalize_xyz, want_stats=Fa
         raise RuntimeError("wx must be (C,3) and new_xyz (B,M,3)")
     z0 = torch.empty((B * M * ns, C), dtype=torch.float32, device=xyz.device)
     rel = torch.empty((B * M * ns, 3), dtype=torch.float32, device=xyz.device)
-    chunks = _lib.lib().ptt_sa_z0_rows_stat_chunks(B, M, ns, C) if want_stats else 0
+    chunks = _host("ptt_sa_z0_rows_stat_chunks", B, M, ns, C) if want_stats else 0
     if chunks:
         part = torch.empty((chunks, 2, C), dtype=torch.float64, device=xyz.device)
-        with torch.cuda.device(xyz.device):
-            _lib.check(_lib.lib().ptt_sa_z0_rows_stats_f32(_ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(term), _ptr(wx), wx.stride(0), B, N, M, ns, C,
-                                                           float(radius), int(bool(normalize_xyz)), _ptr(z0), _ptr(rel), _ptr(part), part.numel(),
-                                                           _stream()), "ptt_sa_z0_rows_stats_f32")
+        _launch("ptt_sa_z0_rows_stats_f32", xyz.device, _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(term), _ptr(wx), wx.stride(0), B, N, M, ns, C,
+                float(radius), int(bool(normalize_xyz)), _ptr(z0), _ptr(rel), _ptr(part), part.numel())
         return z0, rel, part
-    with torch.cuda.device(xyz.device):
-        _lib.check(_lib.lib().ptt_sa_z0_rows_f32(_ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(term), _ptr(wx), wx.stride(0), B, N, M, ns, C, float(radius),
-                                                 int(bool(normalize_xyz)), _ptr(z0), _ptr(rel), _stream()), "ptt_sa_z0_rows_f32")
+    _launch("ptt_sa_z0_rows_f32", xyz.device, _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(term), _ptr(wx), wx.stride(0), B, N, M, ns, C, float(radius),
+            int(bool(normalize_xyz)), _ptr(z0), _ptr(rel))
     return (z0, rel, None) if want_stats else (z0, rel)
 
 
@@ -1622,13 +1510,11 @@ def sa_z0_bnbwd(part, g, z0, rel, mean, invstd, gamma, act_scale, act_shift, wan
     dev = g.device
     d_wx = torch.empty((C, 3), dtype=torch.float32, device=dev) if not dwx_partials else None
     dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(2))
-    ws = _ws(_lib.lib().ptt_sa_z0_bnbwd_workspace(R, C), dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ptt_sa_z0_bnbwd_f32(_ptr(part), part.shape[0], _ptr(g), _ptr(z0), _ptr(rel), _ptr(mean), _ptr(invstd), _ptr(gamma),
-                                                  _ptr(act_scale), _ptr(act_shift), R, C, _ptr(g) if want_dz else None, _ptr(d_wx), _ptr(dgamma),
-                                                  _ptr(dbeta), _ptr(ws), ws.numel() * 8, _stream()), "ptt_sa_z0_bnbwd_f32")
+    ws, ws_arg = _workspace("ptt_sa_z0_bnbwd_workspace", dev, R, C)
+    _launch("ptt_sa_z0_bnbwd_f32", dev, _ptr(part), part.shape[0], _ptr(g), _ptr(z0), _ptr(rel), _ptr(mean), _ptr(invstd), _ptr(gamma),
+            _ptr(act_scale), _ptr(act_shift), R, C, _ptr(g) if want_dz else None, _ptr(d_wx), _ptr(dgamma), _ptr(dbeta), *ws_arg)
     if dwx_partials:
-        d_wx = (ws, _lib.lib().ptt_sa_z0_bnbwd_workspace(R, C) // (12 * C))
+        d_wx = (ws, _host("ptt_sa_z0_bnbwd_workspace", R, C) // (12 * C))
     return (g if want_dz else None), d_wx, dgamma, dbeta
 
 
@@ -1639,8 +1525,7 @@ def scatter_csr(idx, N):
     B, E = idx.shape
     order = torch.empty((B, E), dtype=torch.int32, device=idx.device)
     start = torch.empty((B, int(N) + 1), dtype=torch.int32, device=idx.device)
-    with torch.cuda.device(idx.device):
-        _lib.check(_lib.lib().ptt_scatter_csr_i32(_ptr(idx), B, int(N), E, _ptr(order), _ptr(start), _stream()), "ptt_scatter_csr_i32")
+    _launch("ptt_scatter_csr_i32", idx.device, _ptr(idx), B, int(N), E, _ptr(order), _ptr(start))
     return order, start
 
 
@@ -1653,23 +1538,20 @@ def scatter_rows_det(g, idx, N, csr=None, minuend=None, negate=False):
     B, E, C = g.shape
     order, start = csr if csr is not None else scatter_csr(idx, N)
     out = torch.empty((B, int(N), C), dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        if minuend is None and not negate:
-            _lib.check(_lib.lib().ptt_scatter_rows_csr_f32(_ptr(g), _ptr(order), _ptr(start), B, int(N), E, C, _ptr(out), _stream()),
-                       "ptt_scatter_rows_csr_f32")
-        else:
-            if minuend is not None:
-                _chk(minuend, "minuend", torch.float32, 3)
-                if tuple(minuend.shape) != (B, int(N), C):
-                    raise ValueError("minuend: (B,N,C) expected")
-            _lib.check(_lib.lib().ptt_scatter_rows_csr_sub_f32(_ptr(g), _ptr(order), _ptr(start), B, int(N), E, C, _ptr(minuend), _ptr(out),
-                                                               _stream()), "ptt_scatter_rows_csr_sub_f32")
+    if minuend is None and not negate:
+        _launch("ptt_scatter_rows_csr_f32", g.device, _ptr(g), _ptr(order), _ptr(start), B, int(N), E, C, _ptr(out))
+    else:
+        if minuend is not None:
+            _chk(minuend, "minuend", torch.float32, 3)
+            if tuple(minuend.shape) != (B, int(N), C):
+                raise ValueError("minuend: (B,N,C) expected")
+        _launch("ptt_scatter_rows_csr_sub_f32", g.device, _ptr(g), _ptr(order), _ptr(start), B, int(N), E, C, _ptr(minuend), _ptr(out))
     return out
 
 
 def rows_gemm_rsum16_supported(x, K, N):
     return bool(x.dim() == 2 and x.stride(1) == 1 and x.data_ptr() % 16 == 0
-                and _lib.lib().ptt_rows_gemm_rsum16_supported(x.shape[0], int(K), int(N), x.stride(0)))
+                and _host("ptt_rows_gemm_rsum16_supported", x.shape[0], int(K), int(N), x.stride(0)))
 
 
 def rows_gemm_rsum16(x, wpacked, N, residual):
@@ -1681,16 +1563,14 @@ def rows_gemm_rsum16(x, wpacked, N, residual):
         raise ValueError("rows_gemm_rsum16: residual (rows, N) expected")
     out, plain = (torch.empty((rows, int(N)), dtype=torch.float32, device=x.device) for _ in range(2))
     gsum = torch.empty((rows // 16, int(N)), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_rsum16_f32(_ptr(x), rows, K, x.stride(0), _ptr(wpacked), int(N), _ptr(residual), residual.stride(0),
-                                                       _ptr(out), int(N), _ptr(plain), int(N), _ptr(gsum), int(N), _stream()),
-                   "ptt_rows_gemm_rsum16_f32")
+    _launch("ptt_rows_gemm_rsum16_f32", x.device, _ptr(x), rows, K, x.stride(0), _ptr(wpacked), int(N), _ptr(residual), residual.stride(0), _ptr(out),
+            int(N), _ptr(plain), int(N), _ptr(gsum), int(N), timed='ptt_linear_f32')
     return plain, out, gsum
 
 
 def rows_gemm_rsum16_heads_supported(x, D, hd):
     return bool(x.dim() == 2 and x.stride(1) == 1 and x.data_ptr() % 16 == 0 and x.shape[1] == int(D)
-                and _lib.lib().ptt_rows_gemm_rsum16_heads_supported(x.shape[0], int(D), int(hd), x.stride(0)))
+                and _host("ptt_rows_gemm_rsum16_heads_supported", x.shape[0], int(D), int(hd), x.stride(0)))
 
 
 def rows_gemm_rsum16_heads(x, wpacked, hd, residual):
@@ -1705,10 +1585,8 @@ def rows_gemm_rsum16_heads(x, wpacked, hd, residual):
         raise ValueError("rows_gemm_rsum16_heads: D %% hd == 0 and a packed hd x hd weight expected (D=%d hd=%d)" % (D, hd))
     out, plain = (torch.empty((rows, D), dtype=torch.float32, device=x.device) for _ in range(2))
     gsum = torch.empty((rows // 16, D), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _timed('ptt_linear_f32'):
-        _lib.check(_lib.lib().ptt_rows_gemm_rsum16_heads_f32(_ptr(x), rows, D, hd, x.stride(0), _ptr(wpacked), _ptr(residual),
-                                                             residual.stride(0), _ptr(out), D, _ptr(plain), D, _ptr(gsum), D, _stream()),
-                   "ptt_rows_gemm_rsum16_heads_f32")
+    _launch("ptt_rows_gemm_rsum16_heads_f32", x.device, _ptr(x), rows, D, hd, x.stride(0), _ptr(wpacked), _ptr(residual), residual.stride(0),
+            _ptr(out), D, _ptr(plain), D, _ptr(gsum), D, timed='ptt_linear_f32')
     return plain, out, gsum
 
 
@@ -1726,11 +1604,9 @@ def layernorm_train_fwd(x, weight, bias, eps, residual=None):
             raise ValueError("layernorm_train_fwd: residual (rows, C) expected")
     y = torch.empty((rows, C), dtype=torch.float32, device=x.device)
     mean, rstd = (torch.empty((rows,), dtype=torch.float32, device=x.device) for _ in range(2))
-    with torch.cuda.device(x.device), _timed('ptt_layernorm_train_fwd_f32'):
-        _lib.check(_lib.lib().ptt_layernorm_train_fwd_f32(_ptr(x), rows, C, x.stride(0) if rows > 1 else C, _ptr(weight), _ptr(bias),
-                                                          float(eps), _ptr(residual),
-                                                          (residual.stride(0) if (residual is not None and rows > 1) else C),
-                                                          _ptr(y), C, _ptr(mean), _ptr(rstd), _stream()), "ptt_layernorm_train_fwd_f32")
+    _launch("ptt_layernorm_train_fwd_f32", x.device, _ptr(x), rows, C, x.stride(0) if rows > 1 else C, _ptr(weight), _ptr(bias), float(eps),
+            _ptr(residual), (residual.stride(0) if (residual is not None and rows > 1) else C), _ptr(y), C, _ptr(mean), _ptr(rstd),
+            timed='ptt_layernorm_train_fwd_f32')
     return y, mean, rstd
 
 
@@ -1748,11 +1624,9 @@ def layernorm_bwd(dy, x, mean, rstd, weight):
     dw, db = (torch.empty((C,), dtype=torch.float32, device=x.device) for _ in range(2))
     if rows == 0:
         return dx, dw.zero_(), db.zero_()
-    ws = _ws(_lib.lib().ptt_layernorm_bwd_workspace(rows, C), x.device)
-    with torch.cuda.device(x.device), _timed('ptt_layernorm_bwd_f32'):
-        _lib.check(_lib.lib().ptt_layernorm_bwd_f32(_ptr(dy), dy.stride(0) if rows > 1 else C, _ptr(x), x.stride(0) if rows > 1 else C,
-                                                    _ptr(mean), _ptr(rstd), _ptr(weight), rows, C, _ptr(dx), C, _ptr(dw), _ptr(db),
-                                                    _ptr(ws), ws.numel() * 8, _stream()), "ptt_layernorm_bwd_f32")
+    ws, ws_arg = _workspace("ptt_layernorm_bwd_workspace", x.device, rows, C)
+    _launch("ptt_layernorm_bwd_f32", x.device, _ptr(dy), dy.stride(0) if rows > 1 else C, _ptr(x), x.stride(0) if rows > 1 else C, _ptr(mean),
+            _ptr(rstd), _ptr(weight), rows, C, _ptr(dx), C, _ptr(dw), _ptr(db), *ws_arg, timed='ptt_layernorm_bwd_f32')
     return dx, dw, db
 
 
@@ -1762,9 +1636,7 @@ def pt_pair_input(q, kf, knn, pos):
     B, N, D = q.shape
     k = knn.shape[2]
     t = torch.empty((B, N, k, D), dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        _lib.check(_lib.lib().ptt_pt_pair_input_f32(_ptr(q), _ptr(kf), _ptr(knn), _ptr(pos), B, N, k, D, _ptr(t), _stream()),
-                   "ptt_pt_pair_input_f32")
+    _launch("ptt_pt_pair_input_f32", q.device, _ptr(q), _ptr(kf), _ptr(knn), _ptr(pos), B, N, k, D, _ptr(t))
     return t
 
 
@@ -1773,9 +1645,7 @@ def pt_pair_input_qkv(qkv, knn, pos, D):
     B, N, _ = qkv.shape
     k = knn.shape[2]
     t = torch.empty((B, N, k, D), dtype=torch.float32, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _lib.check(_lib.lib().ptt_pt_pair_input_ld_f32(qkv.data_ptr(), 3 * D, qkv.data_ptr() + 4 * D, 3 * D, _ptr(knn), _ptr(pos), B, N, k,
-                                                       D, _ptr(t), _stream()), "ptt_pt_pair_input_ld_f32")
+    _launch("ptt_pt_pair_input_ld_f32", qkv.device, qkv.data_ptr(), 3 * D, qkv.data_ptr() + 4 * D, 3 * D, _ptr(knn), _ptr(pos), B, N, k, D, _ptr(t))
     return t
 
 
@@ -1785,9 +1655,8 @@ def pt_attn_fwd_qkv(a, qkv, knn, pos, D, scale, want_attn=False):
     B, N, k, _ = a.shape
     res = torch.empty((B, N, D), dtype=torch.float32, device=a.device)
     attn = torch.empty_like(a) if want_attn else None
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().ptt_pt_attn_fwd_ld_f32(_ptr(a), qkv.data_ptr() + 8 * D, 3 * D, _ptr(knn), _ptr(pos), B, N, k, D, float(scale),
-                                                     _ptr(attn), _ptr(res), _stream()), "ptt_pt_attn_fwd_ld_f32")
+    _launch("ptt_pt_attn_fwd_ld_f32", a.device, _ptr(a), qkv.data_ptr() + 8 * D, 3 * D, _ptr(knn), _ptr(pos), B, N, k, D, float(scale), _ptr(attn),
+            _ptr(res))
     return res, attn
 
 
@@ -1796,9 +1665,7 @@ def pt_attn_train_fwd(a, vf, knn, pos, scale):
     B, N, k, D = a.shape
     attn = torch.empty_like(a)
     res = torch.empty((B, N, D), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().ptt_pt_attn_train_fwd_f32(_ptr(a), _ptr(vf), _ptr(knn), _ptr(pos), B, N, k, D, float(scale), _ptr(attn),
-                                                        _ptr(res), _stream()), "ptt_pt_attn_train_fwd_f32")
+    _launch("ptt_pt_attn_train_fwd_f32", a.device, _ptr(a), _ptr(vf), _ptr(knn), _ptr(pos), B, N, k, D, float(scale), _ptr(attn), _ptr(res))
     return attn, res
 
 
@@ -1806,9 +1673,8 @@ def pt_attn_train_bwd(attn, vf, knn, pos, dres, scale):
     """-> (da, dvp), both (B,N,k,D)."""
     B, N, k, D = attn.shape
     da, dvp = torch.empty_like(attn), torch.empty_like(attn)
-    with torch.cuda.device(attn.device):
-        _lib.check(_lib.lib().ptt_pt_attn_train_bwd_f32(_ptr(attn), _ptr(vf), _ptr(knn), _ptr(pos), _ptr(dres), B, N, k, D, float(scale),
-                                                        _ptr(da), _ptr(dvp), _stream()), "ptt_pt_attn_train_bwd_f32")
+    _launch("ptt_pt_attn_train_bwd_f32", attn.device, _ptr(attn), _ptr(vf), _ptr(knn), _ptr(pos), _ptr(dres), B, N, k, D, float(scale), _ptr(da),
+            _ptr(dvp))
     return da, dvp
 
 
@@ -1910,8 +1776,7 @@ def row_jobs(jobs):
     n = len(jobs)
     arr = (_lib.RowJob * n)(*[j for j, _ in jobs])
     dev = jobs[0][1][0].device
-    with torch.cuda.device(dev), _timed('ptt_linear_f32'):
-        _lib.check(_lib.lib().ptt_row_jobs_f32(arr, n, _stream()), "ptt_row_jobs_f32")
+    _launch("ptt_row_jobs_f32", dev, arr, n, timed='ptt_linear_f32')
 
 
 def sa_levels_point_jobs(xyz, inds0, npoints, radii, nsamples, knn_k=0):
@@ -1947,8 +1812,7 @@ def sa_levels_point_jobs(xyz, inds0, npoints, radii, nsamples, knn_k=0):
         j.idx_out, j.rel_out = kidx.data_ptr(), rel.data_ptr()
         j.kind, j.sel_ld, j.B, j.Nraw, j.Npts, j.M, j.nsample, j.radius = 1, inds0.shape[1], B, N, M, M, int(knn_k), 0.0
         knn = (kidx, rel)
-    with torch.cuda.device(dev), _timed('ptt_ball_query_f32'):
-        _lib.check(_lib.lib().ptt_point_jobs_f32(arr, n_jobs, _stream()), "ptt_point_jobs_f32")
+    _launch("ptt_point_jobs_f32", dev, arr, n_jobs, timed='ptt_ball_query_f32')
     return levels, inds64, knn
 
 
@@ -1965,9 +1829,8 @@ def fps_ball_knn(xyz, npoint, radius, nsample, k=0):
     idx = torch.empty((B, M, int(nsample)), dtype=torch.int32, device=dev)
     knn = torch.empty((B, M, int(k)), dtype=torch.int32, device=dev) if k else None
     rel = torch.empty((B, M, int(k), 3), dtype=torch.float32, device=dev) if k else None
-    with torch.cuda.device(dev), _timed('ptt_fps_f32'):
-        _lib.check(_lib.lib().ptt_fps_ball_knn_f32(_ptr(xyz), B, N, M, float(radius), int(nsample), int(k), _ptr(inds), _ptr(inds64),
-                                                   _ptr(new_xyz), _ptr(idx), _ptr(knn), _ptr(rel), _stream()), "ptt_fps_ball_knn_f32")
+    _launch("ptt_fps_ball_knn_f32", dev, _ptr(xyz), B, N, M, float(radius), int(nsample), int(k), _ptr(inds), _ptr(inds64), _ptr(new_xyz), _ptr(idx),
+            _ptr(knn), _ptr(rel), timed='ptt_fps_f32')
     return inds, inds64, new_xyz, idx, ((knn, rel) if k else None)
 
 
@@ -2001,8 +1864,7 @@ def track_losses(seed_cls, cls_label, search_inds, votes, reg_label, box_data, c
     d = _track_loss_desc(seed_cls, cls_label, search_inds, votes, reg_label, box_data, centres, pw_seed, pw_box, weights)
     out = torch.empty((8,), dtype=torch.float32, device=seed_cls.device)
     total = torch.empty((), dtype=torch.float32, device=seed_cls.device)
-    with torch.cuda.device(seed_cls.device):
-        _lib.check(_lib.lib().ptt_track_losses_f32(ctypes.byref(d), _ptr(out), _ptr(total), _stream()), "ptt_track_losses_f32")
+    _launch("ptt_track_losses_f32", seed_cls.device, ctypes.byref(d), _ptr(out), _ptr(total))
     return total, out
 
 
@@ -2012,9 +1874,7 @@ def track_losses_bwd(out8, upstream, seed_cls, cls_label, search_inds, votes, re
     if upstream is not None and (upstream.dtype != torch.float32 or upstream.numel() != 1 or not upstream.is_cuda):
         raise ValueError("upstream: one float32 on the device expected")
     g_cls, g_votes, g_box = torch.empty_like(seed_cls), torch.empty_like(votes), torch.empty_like(box_data)
-    with torch.cuda.device(seed_cls.device):
-        _lib.check(_lib.lib().ptt_track_losses_bwd_f32(ctypes.byref(d), _ptr(out8), _ptr(upstream), _ptr(g_cls), _ptr(g_votes), _ptr(g_box),
-                                                       _stream()), "ptt_track_losses_bwd_f32")
+    _launch("ptt_track_losses_bwd_f32", seed_cls.device, ctypes.byref(d), _ptr(out8), _ptr(upstream), _ptr(g_cls), _ptr(g_votes), _ptr(g_box))
     return g_cls, g_votes, g_box
 
 
@@ -2025,7 +1885,7 @@ class AdamTable(object):
 
     def __init__(self, params, exp_avgs, exp_avg_sqs):
         self.device = params[0].device
-        chunk = _lib.lib().ptt_adam_chunk_elems()
+        chunk = _host("ptt_adam_chunk_elems")
         n = len(params)
         self.host = torch.zeros((n, ctypes.sizeof(_lib.AdamTensor)), dtype=torch.uint8).pin_memory()
         self.rows = (_lib.AdamTensor * n).from_address(self.host.data_ptr())
@@ -2062,10 +1922,8 @@ class AdamTable(object):
             self.uploaded.record()
             self.grad_ptrs = ptrs
         h = self.hyper(beta1, beta2, eps, step_size, bias2_sqrt, weight_decay, max_norm, write_clipped)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ptt_adam_clip_step_f32(_ptr(self.table), _ptr(self.which), _ptr(self.first), self.n_chunks, ctypes.byref(h),
-                                                         _ptr(self.partial), self.partial.numel(), _ptr(self.norm), _stream()),
-                       "ptt_adam_clip_step_f32")
+        _launch("ptt_adam_clip_step_f32", self.device, _ptr(self.table), _ptr(self.which), _ptr(self.first), self.n_chunks, ctypes.byref(h),
+                _ptr(self.partial), self.partial.numel(), _ptr(self.norm))
         return self.norm
 
     @staticmethod
@@ -2082,10 +1940,8 @@ class AdamTable(object):
         a captured training step records. The gradients are the ones the last step() uploaded (check_grads_in_place)."""
         if self.grad_ptrs is None:
             raise RuntimeError("AdamTable.step_device_hyper: step() must have run once (the gradient addresses are uploaded then)")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ptt_adam_clip_step_dev_f32(_ptr(self.table), _ptr(self.which), _ptr(self.first), self.n_chunks, _ptr(hyper_device),
-                                                             1 if clip else 0, _ptr(self.partial), self.partial.numel(), _ptr(self.norm), _stream()),
-                       "ptt_adam_clip_step_dev_f32")
+        _launch("ptt_adam_clip_step_dev_f32", self.device, _ptr(self.table), _ptr(self.which), _ptr(self.first), self.n_chunks, _ptr(hyper_device),
+                1 if clip else 0, _ptr(self.partial), self.partial.numel(), _ptr(self.norm))
         return self.norm
 
 
@@ -2121,9 +1977,7 @@ def unit_rows_eps(x, eps):
     B, C, n = x.shape
     unit = torch.empty((B, n, C), dtype=torch.float32, device=x.device)
     nrm = torch.empty((B, n), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ptt_unit_rows_f32(_ptr(x), x.stride(0), x.stride(2), x.stride(1), B, n, C, float(eps), _ptr(unit), _ptr(nrm),
-                                                _stream()), "ptt_unit_rows_f32")
+    _launch("ptt_unit_rows_f32", x.device, _ptr(x), x.stride(0), x.stride(2), x.stride(1), B, n, C, float(eps), _ptr(unit), _ptr(nrm))
     return unit, nrm
 
 
@@ -2140,7 +1994,6 @@ def cos_bwd_rows(A, unit, nrm, G, cosm, own_is_row, like):
         raise ValueError("cos_bwd_rows: shapes")
     dx = torch.empty_strided(like[0], like[1], dtype=torch.float32, device=unit.device)
     own, other, m = (n1, 1, n1) if own_is_row else (1, n1, n2)
-    with torch.cuda.device(unit.device):
-        _lib.check(_lib.lib().ptt_cos_bwd_rows_f32(_ptr(A), _ptr(unit), _ptr(nrm), _ptr(G), _ptr(cosm), n2 * n1, own, other, m, B, n, C, _ptr(dx),
-                                                   dx.stride(0), dx.stride(2), dx.stride(1), _stream()), "ptt_cos_bwd_rows_f32")
+    _launch("ptt_cos_bwd_rows_f32", unit.device, _ptr(A), _ptr(unit), _ptr(nrm), _ptr(G), _ptr(cosm), n2 * n1, own, other, m, B, n, C, _ptr(dx),
+            dx.stride(0), dx.stride(2), dx.stride(1))
     return dx

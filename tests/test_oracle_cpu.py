@@ -172,6 +172,70 @@ def test_library_exports_every_declared_symbol():
     assert lib.ptt_version() == version == _lib.ABI_VERSION
 
 
+def test_binding_signatures_are_the_header_prototypes():
+    """ptt_amd/_lib.py derives restype / argtypes from include/ptt_hip.h (no device, no library load): literal expectations for
+    prototypes that between them use every entry of the type mapping, a (void) list, both non-int return types and a prototype
+    spread over several lines."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_size_t, c_uint32, c_void_p
+    from ptt_amd import _lib
+    vp, i = c_void_p, c_int
+    expect = {
+        "ptt_cosine_map_f32": (c_int, [vp, c_int64, c_int64, c_int64, vp, c_int64, c_int64, c_int64, i, i, i, i, c_float, vp, vp]),
+        "ptt_track_crop_bounds": (c_int, [vp, i, c_double, c_double, vp, vp, i]),                  # struct pointers, double
+        "ptt_mt19937_fill": (c_int, [c_uint32, vp, i]),
+        "ptt_sa_z0_bnbwd_workspace": (c_size_t, [c_longlong, i]),
+        "ptt_adam_chunk_elems": (c_int, []),
+        "ptt_error_name": (c_char_p, [i]),
+        "ptt_fps_ws_f32": (c_int, [vp, i, i, i, vp, vp, c_size_t, vp]),                           # two lines in the header, stream last
+        "ptt_version": (c_int, []),
+    }
+    header = open(os.path.join(ROOT, "include", "ptt_hip.h")).read()
+    assert re.search(r"ptt_fps_ws_f32\([^)]*\n[^)]*\)", header)
+    for name, sig in expect.items():
+        assert _lib.PROTOTYPES[name] == sig, (name, _lib.PROTOTYPES[name])
+    # the header has no scalar int32_t parameter today: the mapping's entry is exercised on a text of its own
+    assert _lib.parse_prototypes("/* c */ int ptt_x(int32_t n,\n const int32_t* p, ptt_stream_t s);  // d\n") == {"ptt_x": (c_int, [c_int32, vp, vp])}
+    used = {t for r, a in list(expect.values()) + [(c_int, [c_int32])] for t in [r] + a}
+    assert used >= set(_lib.CTYPES.values())
+    assert set(_lib.CTYPES) == {"int", "int32_t", "uint32_t", "int64_t", "long long", "size_t", "float", "double", "ptt_stream_t"}
+    assert _lib.parse_defines(header)["PTT_ABI_VERSION"] == _lib.ABI_VERSION
+    assert (_lib.PTT_SA_MAX_LAYERS, _lib.PTT_MAX_SEGMENTS, _lib.PTT_CROP_JOBS_BY_VALUE_MAX) == (4, 4, 8)
+
+
+def test_every_call_in_ops_names_a_prototype_with_that_many_parameters():
+    """ops.py calls the entry points by name: each _launch / _host / _host_checked / _workspace site names a declared function and
+    passes as many arguments as its prototype has (the stream _launch appends and the two of `*ws_arg` counted)."""
+    import ast
+    from ptt_amd import _lib
+    tree = ast.parse(open(os.path.join(ROOT, "ptt_amd", "ops.py")).read())
+    skip = {"_launch": 2, "_host": 1, "_host_checked": 1, "_workspace": 2}            # leading (name[, device]) arguments
+    sites = 0
+    for node in ast.walk(tree):
+        if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in skip):
+            continue
+        first = node.args[0]
+        if isinstance(first, ast.Name):                                                 # the helpers' own bodies pass `name` on
+            continue
+        names = [first.value] if isinstance(first, ast.Constant) else [first.body.value, first.orelse.value]
+        given = sum(2 if isinstance(a, ast.Starred) else 1 for a in node.args[skip[node.func.id]:]) + (node.func.id == "_launch")
+        for name in names:
+            assert name in _lib.PROTOTYPES, (node.lineno, name)
+            assert given == len(_lib.PROTOTYPES[name][1]), (node.lineno, name, given, len(_lib.PROTOTYPES[name][1]))
+            if node.func.id == "_launch":
+                assert _lib.PROTOTYPES[name][0] is ctypes.c_int
+        sites += 1
+    assert sites > 100
+
+
+@pytest.mark.parametrize("text", ["int ptt_ok(int a);\nint ptt_bad(const float* x, unsigned n, ptt_stream_t stream);",
+                                  "short ptt_bad(int a);", "float* ptt_bad(void);", "int ptt_bad(ptt_track_box box);"])
+def test_binding_refuses_a_type_it_does_not_map(text):
+    """A parameter or return type outside the mapping raises and names the prototype; nothing defaults to int."""
+    from ptt_amd import _lib
+    with pytest.raises(RuntimeError, match="ptt_bad"):
+        _lib.parse_prototypes(text)
+
+
 def test_product_path_never_imports_the_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "ptt_amd")):
         for fn in files:
@@ -311,7 +375,8 @@ def test_ctypes_structures_match_the_c_header(tmp_path):
              ("ptt_attn_desc", _lib.AttnDesc), ("ptt_sa_layer", _lib.SaLayer), ("ptt_crop_job", _lib.CropJob),
              ("ptt_regularize_job", _lib.RegularizeJob), ("ptt_pack_job", _lib.PackJob), ("ptt_bn_train_tail", _lib.BnTrainTail),
              ("ptt_track_loss_desc", _lib.TrackLossDesc), ("ptt_adam_tensor", _lib.AdamTensor), ("ptt_adam_hyper", _lib.AdamHyper),
-             ("ptt_bn_bwd_input", _lib.BnBwdInput), ("ptt_grad_job", _lib.GradJob), ("ptt_grad_segment", _lib.GradSegment)]
+             ("ptt_bn_bwd_input", _lib.BnBwdInput), ("ptt_grad_job", _lib.GradJob), ("ptt_grad_segment", _lib.GradSegment),
+             ("ptt_track_box", _lib.TrackBox)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ptt_hip.h"', 'int main(void) {']
     for cname, st in pairs:
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

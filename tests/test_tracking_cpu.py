@@ -102,6 +102,20 @@ def test_job_tables_mirror_the_c_structs():
     np.testing.assert_array_equal(draws, np.random.randint(0, 2 ** 32, 64, dtype=np.uint32))
 
 
+def test_numpy_job_dtypes_are_the_ctypes_structures():
+    """ops.CROP_JOB / REGULARIZE_JOB / TRACK_BOX: field names, offsets and sizes of the ctypes classes (which gcc checks)."""
+    import ctypes
+    from ptt_amd import _lib, ops
+    for dt, st in ((ops.CROP_JOB, _lib.CropJob), (ops.REGULARIZE_JOB, _lib.RegularizeJob), (ops.TRACK_BOX, _lib.TrackBox)):
+        assert list(dt.names) == [name for name, *_ in st._fields_]
+        assert [dt.fields[name][1] for name in dt.names] == [getattr(st, name).offset for name in dt.names]
+        assert [dt.fields[name][0].itemsize for name in dt.names] == [getattr(st, name).size for name in dt.names]
+        assert dt.itemsize == ctypes.sizeof(st)
+    assert (ops.CROP_JOB.itemsize, ops.REGULARIZE_JOB.itemsize, ops.TRACK_BOX.itemsize) == (392, 104, 80)
+    assert ops.CROP_JOB.fields["rot"][0] == np.dtype(("<f8", (9,))) and ops.TRACK_BOX.fields["quat"][0] == np.dtype(("<f8", (4,)))
+    assert ops.CROP_JOBS_BY_VALUE_MAX == _lib.PTT_CROP_JOBS_BY_VALUE_MAX == 8
+
+
 def test_c_host_box_math_equals_the_numpy_restatement():
     """ptt_track_crop_bounds / ptt_track_box_by_offset (the per-step host helpers TrackletRunner calls) against
     box_math.py on 48 random boxes, incl. the redraw branch with the generator position bookkeeping."""
