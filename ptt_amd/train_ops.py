@@ -21,6 +21,7 @@ Every reduction runs in a fixed order: a step is bit-reproducible run to run (te
 """
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.distributed as dist
@@ -42,30 +43,35 @@ def _raw_pointer_ready(conv, bn, device):
     return all(t is not None and t.dtype == torch.float32 and t.device == device and t.is_contiguous() for t in ts)
 
 
+def _pointwise_conv(conv, conv_cls, one):
+    """A k = 1 convolution of class `conv_cls` with unit stride, no padding, one group; one = (1, 1) / (1,)."""
+    return (isinstance(conv, conv_cls) and conv.kernel_size == one and conv.stride == one and conv.padding == (0,) * len(one)
+            and conv.groups == 1)
+
+
+def _conv_bn_relu_unit(unit, conv_cls, bn_cls, one, device):
+    """A [conv k=1 (no bias) -> BatchNorm -> ReLU] unit as SharedMLP and the heads' Conv1d stacks build it, in a state the row
+    kernels take: the BatchNorm in training mode with affine parameters and running statistics, output channels a multiple of 4."""
+    conv = getattr(unit, 'conv', None)
+    bn = getattr(getattr(unit, 'normlayer', None), 'bn', None)
+    if not _pointwise_conv(conv, conv_cls, one) or conv.bias is not None or conv.weight.shape[0] % 4:
+        return False
+    if not isinstance(bn, (bn_cls, nn.SyncBatchNorm)) or not bn.affine or not bn.track_running_stats or bn.momentum is None:
+        return False
+    # a BatchNorm frozen inside a training model (bn.eval(): fine-tuning) normalises with its RUNNING statistics and
+    # must not have them updated — the row kernels use batch statistics, so such a stack takes the stock path
+    if not bn.training:
+        return False
+    if not isinstance(getattr(unit, 'activation', None), nn.ReLU) or list(unit._modules.keys()) != ['conv', 'normlayer', 'activation']:
+        return False
+    return _raw_pointer_ready(conv, bn, device)
+
+
 def usable(mlp, x):
     """Plain SharedMLP units, float32 on a HIP device, training mode."""
     if not (mlp.training and x.is_cuda and x.dtype == torch.float32 and len(mlp) > 0):
         return False
-    for unit in mlp:
-        conv = getattr(unit, 'conv', None)
-        bn = getattr(getattr(unit, 'normlayer', None), 'bn', None)
-        if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (1, 1) or conv.bias is not None or conv.weight.shape[0] % 4:
-            return False
-        if conv.stride != (1, 1) or conv.padding != (0, 0) or conv.dilation != (1, 1) or conv.groups != 1:
-            return False
-        if not isinstance(bn, (nn.BatchNorm2d, nn.SyncBatchNorm)) or not bn.affine or not bn.track_running_stats or bn.momentum is None:
-            return False
-        # a BatchNorm frozen inside a training model (bn.eval(): fine-tuning) normalises with its RUNNING statistics and
-        # must not have them updated — the row kernels use batch statistics, so such a stack takes the stock path
-        if not bn.training:
-            return False
-        if not isinstance(getattr(unit, 'activation', None), nn.ReLU):
-            return False
-        if list(unit._modules.keys()) != ['conv', 'normlayer', 'activation']:
-            return False
-        if not _raw_pointer_ready(conv, bn, x.device):
-            return False
-    return True
+    return all(_conv_bn_relu_unit(unit, nn.Conv2d, nn.BatchNorm2d, (1, 1), x.device) and unit.conv.dilation == (1, 1) for unit in mlp)
 
 
 _pack_cache = {}       # id(parameter tensor) -> (weak reference to it, {(offset, shape, stride, version, transposed): packed})
@@ -144,7 +150,6 @@ class _PackPlan:
 
 FUSED_BN_BWD = os.environ.get("PTT_FUSED_BN_BWD", "1") != "0"     # a layer's BatchNorm + ReLU backward applied by its input-gradient GEMM
 #                                                                  (dev A/B: 0 = the apply pass of round 4)
-POOL_EPILOGUE = True   # the last layer's max-pool from the extrema its GEMM's epilogue takes (False: a pooling pass over z)
 _pack_plans = {}       # device -> _PackPlan
 PACK_PLAN = True       # False: every weight packed by its own launch (development comparisons)
 
@@ -475,38 +480,155 @@ class _SplitCols(torch.autograd.Function):
         return torch.cat((ga, gb), dim=1), None
 
 
+# What _SharedMlpPool keeps of one layer for its backward pass: the rows the convolution read (x_in) and the deferred activation
+# they still need (relu(x_in * in_a + in_b); None, None for plain rows), the convolution output z, its BatchNorm statistics (mean,
+# invstd), the layer's own activation constants (a, b) and the row count the statistics were taken over.
+_Layer = namedtuple('_Layer', 'x_in in_a in_b z mean invstd a b count')
+# A stage's non-tensor arguments: eps / sync group / BatchNorm module per layer, the front (or None) and how many tensors it takes.
+_StageSpec = namedtuple('_StageSpec', 'ns eps preact sync bns z0_part front n_front')
+
+
+def _saved_layers(t, L):
+    """ctx.saved_tensors of _SharedMlpPool -> (arg, [_Layer per layer], the detached parameters, the front's saved tensors)."""
+    n = len(_Layer._fields)
+    return t[0], [_Layer(*t[1 + n * l:1 + n * (l + 1)]) for l in range(L)], t[1 + n * L:1 + (n + 3) * L], t[1 + (n + 3) * L:]
+
+
+class _XcorrFront(object):
+    """CosineSimAug's layer 0 built inside the stage: z0[b,j,i] = P[b,i] + cos[b,j,i] * w_sim (ops.xcorr_z0). tensors = (P, cos, w_sim),
+    all three kept for the backward pass; gradients in that order."""
+
+    def __init__(self, P, cos, w_sim):
+        self.tensors = (P, cos, w_sim)
+
+    def forward(self, tensors):
+        z0, part = ops.xcorr_z0(*tensors, want_stats=True)
+        return z0, part, tensors
+
+    def backward_fused(self, part, g, lay, gamma, saved, needs):
+        """BatchNorm backward applied while layer 0's ONE consumer reads the gradient (no dz0 tensor) -> (gradients, dgamma, dbeta),
+        or None where the kernel does not take the shape."""
+        if not (lay.mean.shape[0] <= 256 and g.is_contiguous()):
+            return None
+        dP, dcos, dw, dgamma, dbeta = ops.xcorr_z0_bnbwd(part, g, *saved, lay.mean, lay.invstd, gamma, lay.a, lay.b)
+        return (dP, dcos, dw), dgamma, dbeta
+
+    def backward(self, dz, saved, needs):
+        P, cos, w_sim = saved
+        return tuple(ops.xcorr_z0_bwd(dz.contiguous(), cos, w_sim, P.shape[0], cos.shape[1], P.shape[1]))
+
+
+class _SaFront(object):
+    """A hoisted SA level's layer 0 built inside the stage: z0 = term[idx] + Wx ((xyz[idx] - new_xyz) / radius) (ops.sa_z0_rows).
+    tensors = (xyz, new_xyz, idx, per-point term | None, Wx); only idx and the relative coordinates the launch formed are kept for
+    the backward pass, which has gradients for the per-point term and Wx."""
+
+    def __init__(self, radius, normalize_xyz, xyz, new_xyz, idx, term, wx):
+        self.radius, self.normalize_xyz = float(radius), bool(normalize_xyz)
+        self.tensors = (xyz, new_xyz, idx, term, wx)
+
+    def forward(self, tensors):
+        xyz, new_xyz, idx, term, wx = tensors
+        z0, rel, part = ops.sa_z0_rows(xyz.contiguous(), new_xyz.contiguous(), idx, term.contiguous() if term is not None else None,
+                                       wx.detach(), self.radius, self.normalize_xyz, want_stats=True)
+        self.points, self.has_term, self.wx = xyz.shape[1], term is not None, wx      # wx as passed: key of the pack cache / GradSink
+        return z0, part, (idx, rel)
+
+    def _d_term(self, dz, idx):
+        B, M, ns = idx.shape
+        return ops.scatter_rows_det(dz.view(B, M * ns, -1), idx.view(B, M * ns), self.points)
+
+    def backward_fused(self, part, g, lay, gamma, saved, needs):
+        """BatchNorm backward applied while the K = 3 weight gradient (d_wx) reads the gradient; dz0 is written (over g) only for
+        the row scatter of a level with point features -> (gradients, dgamma, dbeta), or None where the kernel does not take the
+        shape."""
+        if not (lay.mean.shape[0] <= 1024 and g.is_contiguous() and lay.z.is_contiguous()):
+            return None
+        idx, rel = saved
+        want_term = self.has_term and needs[3]
+        sink, loc = _sunk(self.wx)
+        dz, d_wx, dgamma, dbeta = ops.sa_z0_bnbwd(part, g, lay.z, rel, lay.mean, lay.invstd, gamma, lay.a, lay.b, want_term,
+                                                  dwx_partials=sink is not None)
+        if sink is not None:
+            sink.push(loc, *d_wx)
+            d_wx = None
+        d_term = self._d_term(dz, idx) if want_term else None
+        return (None, None, None, d_term, d_wx), dgamma, dbeta
+
+    def backward(self, dz, saved, needs):
+        idx, rel = saved
+        dz = dz.contiguous()
+        d_term = self._d_term(dz, idx) if self.has_term and needs[3] else None
+        return None, None, None, d_term, weight_grad(self.wx, dz, rel)
+
+
+def _bn_backward(lay, gamma, g, pooled, part, group):
+    """The BatchNorm + ReLU backward of one layer -> (dz, dgamma, dbeta). The gradient of the activated output arrives dense (g, which
+    dz then overwrites) or, at the last layer, POOLED: pooled = (dpooled, arg, ns) — max-pool backward, BatchNorm sums and dz are
+    formed from it, the (R, C) gradient of the pooled layer is never written (ptt_bn_bwd_pooled_f32). part: the backward sums as
+    float64 partials, where the GEMM that produced g took them. group: the layer's SyncBatchNorm process group, or None."""
+    z, mean, invstd, a, b = lay.z, lay.mean, lay.invstd, lay.a, lay.b
+    if group is None:
+        if pooled is not None:
+            return ops.bn_bwd_pooled(*pooled, z, mean, invstd, gamma, a, b)
+        if part is not None:
+            return ops.bn_bwd_from_partials(part, g, z, mean, invstd, gamma, a, b, out=g)           # in place over g
+        return ops.bn_bwd(g, None, z, mean, invstd, gamma, out=g, act_scale=a, act_shift=b)          # in place over g
+    # torch's SyncBatchNorm: dgamma / dbeta are the rank's LOCAL sums (DDP averages parameter gradients); dz uses the sums of
+    # all ranks
+    if pooled is not None:
+        sums = ops.bn_bwd_pooled_sums(*pooled, z, mean, invstd, a, b)
+    elif part is not None:
+        sums = ops.bn_bwd_sums_from_partials(part)
+    else:
+        sums = ops.bn_bwd_sums(g, None, z, mean, invstd, act_scale=a, act_shift=b)
+    local = sums.float()
+    dbeta, dgamma = local[0].contiguous(), local[1].contiguous()
+    dist.all_reduce(sums, group=group)
+    glob = sums.float()
+    if pooled is not None:
+        dz = ops.bn_bwd_pooled_apply(*pooled, z, mean, invstd, gamma, glob[0].contiguous(), glob[1].contiguous(), lay.count, a, b)
+    else:
+        dz = ops.bn_bwd_apply(g, None, z, mean, invstd, gamma, glob[0].contiguous(), glob[1].contiguous(), lay.count, out=g,
+                              act_scale=a, act_shift=b)
+    return dz, dgamma, dbeta
+
+
+def _input_grad(dz, w2, prev):
+    """g = dz @ w2, the gradient w.r.t. a layer's input rows -> (g, part). prev: the record of the layer that produced those rows —
+    g is then the gradient ITS BatchNorm receives, and the backward sums of that BatchNorm come out of this GEMM's epilogue (part)
+    where the persistent row GEMM takes the shape; None: the stage's own (not normalised) input rows."""
+    if prev is not None and ops.rows_gemm_supported(dz.shape[0], w2.shape[0], w2.shape[1], dz.stride(0), w2.shape[1], x=dz):
+        return ops.rows_gemm_bnbwd(dz, packed(w2, True), w2.shape[1], prev.z, prev.mean, prev.invstd, prev.a, prev.b)
+    return conv_rows(dz, w2, transpose=True)
+
+
 class _SharedMlpPool(torch.autograd.Function):
-    """(rows (R,C0), ns, eps per layer, preact, [W, gamma, beta] per layer) -> (pooled (R/ns, C_L), [mean, var] per layer).
+    """(rows (R,C0), spec, the front's tensors, [W, gamma, beta] per layer) -> (pooled (R/ns, C_L), [mean, var, count] per layer).
+    spec (_StageSpec): the pool width ns, eps per layer, preact, sync / bns per layer, z0_part, the front.
     preact: `rows` already IS layer 0's convolution output (the caller hoisted that layer: train_ops.sa_level_hoisted /
     xcorr_hoisted), so layer 0 is BatchNorm + ReLU only and its W entry is a placeholder that gets no gradient."""
 
     @staticmethod
-    def forward(ctx, x, ns, eps, preact, sync, bns, z0_part, front, f0, f1, f2, f3, f4, *params):
+    def forward(ctx, x, spec, *tensors):
         """Deferred activation: a layer's output relu(BatchNorm(z)) = relu(z * a + b) is never written — the next
         convolution, its weight gradient, the max-pool and the BatchNorm backward apply it while they load z.
         sync: per layer a torch.distributed process group (nn.SyncBatchNorm: the statistics are those of the rows of ALL
         ranks — one all-reduce of 2C + 1 float64 per layer and direction) or None. bns: per layer the BatchNorm module whose
         bookkeeping (running statistics, batch counter) the launch that forms the statistics does, with the activation
         constants a, b (ops.bn_stats / bn_finish_partials with `bn`), or None: the caller does it (SyncBatchNorm layers).
-        front (with preact, x = None): the rows z0 are built HERE from f0..f4, so that the backward pass can END with one pass over the
-        gradient of the activated z0 that applies layer 0's BatchNorm backward on the fly and feeds z0's consumers directly, instead
-        of an apply pass that writes dz0 and further passes that read it:
-          ('xcorr',): CosineSimAug's layer 0, z0 = f0[b,i] + f1[b,j,i] * f2 (P, cos, w_sim) — ops.xcorr_z0 / ops.xcorr_z0_bnbwd;
-          ('sa', radius, normalize_xyz): a hoisted SA level's layer 0, z0 = f3[idx] + f4 ((f0[idx] - f1) / radius) (xyz, new_xyz, idx,
-          per-point term | None, Wx) — ops.sa_z0_rows / ops.sa_z0_bnbwd."""
+        front (with preact, x = None): an _XcorrFront / _SaFront that builds the rows z0 HERE from the first n_front of `tensors`,
+        so that the backward pass can END with one pass over the gradient of the activated z0 that applies layer 0's BatchNorm
+        backward on the fly and feeds z0's consumers directly (the front's backward_fused), instead of an apply pass that writes
+        dz0 and further passes that read it (the front's backward)."""
         ctx.set_materialize_grads(False)          # the statistics outputs carry no gradient: no zero tensors made for them
+        ns, eps, preact, sync, bns, z0_part, front, n_front = spec
+        params = tensors[n_front:]
         L = len(params) // 3
-        saved, stats, counts = [], [], []
-        ctx.front = front
+        layers, stats = [], []
         front_saved = ()
-        if front is not None and front[0] == 'xcorr':
-            x, z0_part = ops.xcorr_z0(f0, f1, f2, want_stats=True)
-            front_saved = (f0, f1, f2)
-        elif front is not None:
-            x, rel, z0_part = ops.sa_z0_rows(f0.contiguous(), f1.contiguous(), f2, f3.contiguous() if f3 is not None else None, f4.detach(),
-                                             front[1], front[2], want_stats=True)
-            ctx.sa_points, ctx.has_term, ctx.f4 = f0.shape[1], f3 is not None, f4
-            front_saved = (f2, rel)
+        if front is not None:
+            x, z0_part, front_saved = front.forward(tensors[:n_front])
         cur, cur_a, cur_b = x.contiguous(), None, None
         for l in range(L):
             W, gamma, beta = params[3 * l], params[3 * l + 1], params[3 * l + 2]
@@ -514,7 +636,7 @@ class _SharedMlpPool(torch.autograd.Function):
             part, extrema = None, None
             if preact and l == 0:
                 z, part = cur, z0_part                     # the caller's launch summed the statistics of its rows (or None)
-            elif (l == L - 1 and ns > 1 and POOL_EPILOGUE and sync[l] is None and cur_a is not None
+            elif (l == L - 1 and ns > 1 and sync[l] is None and cur_a is not None
                   and ops.rows_gemm_pool_supported(cur.shape[0], cur.shape[1], cout, cur.stride(0), ns, x=cur)):
                 # the last layer: its GEMM's epilogue also takes the per-group extrema of z, so that the max-pool needs no pass
                 # over z once the statistics (summed by the same launch) are finished
@@ -534,144 +656,73 @@ class _SharedMlpPool(torch.autograd.Function):
                 else:
                     mean, var, invstd, a, b = ops.bn_stats(z, eps[l], bn=bns[l])
                 count = _row_count(z.shape[0], z.device)
-            saved += [cur, cur_a if cur_a is not None else mean.new_empty(0), cur_b if cur_b is not None else mean.new_empty(0),
-                      z, mean, invstd, a, b, count]
+            layers.append(_Layer(cur, cur_a, cur_b, z, mean, invstd, a, b, count))
             stats += [mean, var, count]
             cur, cur_a, cur_b = z, a, b
+        # a pooling pass over z where the last GEMM took no extrema (shape not supported, SyncBatchNorm, a one-layer stage)
         pooled, arg = ops.pool_select(extrema, cur_a, cur_b) if extrema is not None else ops.pool_rows(cur, ns, cur_a, cur_b)
-        ctx.save_for_backward(arg, *saved, *[p.detach() for p in params], *front_saved)
+        ctx.save_for_backward(arg, *[t for lay in layers for t in lay], *[p.detach() for p in params], *front_saved)
         ctx.weights = tuple(params[3 * l] for l in range(L))     # the parameter objects themselves: keys of the pack cache
         ctx.param_objs = tuple(params)                           # ... and of a GradSink
-        ctx.L, ctx.ns, ctx.preact, ctx.sync = L, int(ns), bool(preact), tuple(sync)
+        ctx.L, ctx.ns, ctx.preact, ctx.sync, ctx.front, ctx.n_front = L, int(ns), bool(preact), tuple(sync), front, n_front
         ctx.mark_non_differentiable(*stats)
         return (pooled,) + tuple(stats)
 
     @staticmethod
     def backward(ctx, dpooled, *unused):
-        L, ns = ctx.L, ctx.ns
-        t = ctx.saved_tensors
-        arg, saved, params, front = t[0], t[1:1 + 9 * L], t[1 + 9 * L:1 + 12 * L], t[1 + 12 * L:]
+        L, ns, front = ctx.L, ctx.ns, ctx.front
+        arg, layers, params, front_saved = _saved_layers(ctx.saved_tensors, L)
+        front_needs = ctx.needs_input_grad[2:2 + ctx.n_front]      # apply(x, spec, *front tensors, *params)
         dpooled = dpooled.contiguous()
         g, part = None, None        # part: BatchNorm backward sums of THIS layer, taken by the GEMM that produced g
         grads = [None] * (3 * L)
-        front_grads = [None] * 5
-        kind = ctx.front[0] if ctx.front is not None else None
+        front_grads = (None,) * ctx.n_front
         for l in range(L - 1, -1, -1):
-            x_in, in_a, in_b, z, mean, invstd, a, b, count = saved[9 * l:9 * l + 9]
-            W, gamma = params[3 * l], params[3 * l + 1]
-            last = l == L - 1
-            # the last layer's gradient arrives POOLED: max-pool backward, BatchNorm sums and dz are formed from (dpooled,
-            # arg) — the (R, C) gradient of the pooled layer is never written (ptt_bn_bwd_pooled_f32)
+            lay, prev = layers[l], (layers[l - 1] if l > 0 else None)
+            gamma, group = params[3 * l + 1], ctx.sync[l]
+            w2 = ctx.weights[l].reshape(ctx.weights[l].shape[0], -1)
+            last = l == L - 1           # the last layer's gradient arrives POOLED (see _bn_backward)
             fused = None
-            if FUSED_BN_BWD and ctx.sync[l] is None and l > 0 and (last or part is not None):
+            if FUSED_BN_BWD and group is None and l > 0 and (last or part is not None):
                 # the layer's BatchNorm + ReLU backward is applied by its input-gradient GEMM while that stages its rows (three
                 # per-channel constants instead of a pass that reads g and z and writes dz); the GEMM writes dz out once for the
                 # weight gradient, which therefore runs after it
                 src = dpooled if last else g
                 pooled = last and ns > 1
-                w2 = ctx.weights[l].reshape(ctx.weights[l].shape[0], -1)
-                if ops.rows_gemm_bnbwd_fused_supported(z.shape[0], w2.shape[0], w2.shape[1], ns if pooled else 0, src, z):
+                if ops.rows_gemm_bnbwd_fused_supported(lay.z.shape[0], w2.shape[0], w2.shape[1], ns if pooled else 0, src, lay.z):
                     if last:
-                        dgamma, dbeta, consts = ops.bn_bwd_pooled_consts(dpooled, arg, ns, z, mean, invstd, gamma, a, b)
+                        dgamma, dbeta, consts = ops.bn_bwd_pooled_consts(dpooled, arg, ns, lay.z, lay.mean, lay.invstd, gamma, lay.a, lay.b)
                     else:
-                        dgamma, dbeta, consts = ops.bn_bwd_consts(part, mean, invstd, gamma, z.shape[0])
-                    zp, mp, ip, ap, bp = saved[9 * (l - 1) + 3], saved[9 * (l - 1) + 4], saved[9 * (l - 1) + 5], saved[9 * (l - 1) + 6], saved[9 * (l - 1) + 7]
-                    fused = ops.rows_gemm_bnbwd_fused(src, arg if pooled else None, ns if pooled else 0, z, consts, mean, a, b,
-                                                      packed(w2, True), w2.shape[1], zp, mp, ip, ap, bp)
+                        dgamma, dbeta, consts = ops.bn_bwd_consts(part, lay.mean, lay.invstd, gamma, lay.z.shape[0])
+                    fused = ops.rows_gemm_bnbwd_fused(src, arg if pooled else None, ns if pooled else 0, lay.z, consts, lay.mean, lay.a, lay.b,
+                                                      packed(w2, True), w2.shape[1], prev.z, prev.mean, prev.invstd, prev.a, prev.b)
             if fused is not None:
                 g, part, dz = fused
                 grads[3 * l + 1], grads[3 * l + 2] = dgamma, dbeta
-                has_t = in_a.numel() > 0
-                grads[3 * l] = weight_grad(w2, dz, x_in, in_a if has_t else None, in_b if has_t else None)
+                grads[3 * l] = weight_grad(w2, dz, lay.x_in, lay.in_a, lay.in_b)
                 continue
-            if ctx.sync[l] is not None:
-                # torch's SyncBatchNorm: dgamma / dbeta are the rank's LOCAL sums (DDP averages parameter gradients); dz
-                # uses the sums of all ranks
-                if last:
-                    sums = ops.bn_bwd_pooled_sums(dpooled, arg, ns, z, mean, invstd, a, b)
-                elif part is not None:
-                    sums = ops.bn_bwd_sums_from_partials(part)
-                else:
-                    sums = ops.bn_bwd_sums(g, None, z, mean, invstd, act_scale=a, act_shift=b)
-                local = sums.float()
-                dbeta, dgamma = local[0].contiguous(), local[1].contiguous()
-                dist.all_reduce(sums, group=ctx.sync[l])
-                glob = sums.float()
-                if last:
-                    dz = ops.bn_bwd_pooled_apply(dpooled, arg, ns, z, mean, invstd, gamma, glob[0].contiguous(), glob[1].contiguous(),
-                                                 count, a, b)
-                else:
-                    dz = ops.bn_bwd_apply(g, None, z, mean, invstd, gamma, glob[0].contiguous(), glob[1].contiguous(), count, out=g,
-                                          act_scale=a, act_shift=b)
-            elif last:
-                dz, dgamma, dbeta = ops.bn_bwd_pooled(dpooled, arg, ns, z, mean, invstd, gamma, a, b)
-            elif part is not None and l == 0 and ctx.preact and kind == 'xcorr' and mean.shape[0] <= 256 and g.is_contiguous():
-                # CosineSimAug's layer 0: BatchNorm backward applied while its ONE consumer reads the gradient (no dz0 tensor)
-                front_grads[0], front_grads[1], front_grads[2], dgamma, dbeta = ops.xcorr_z0_bnbwd(part, g, front[0], front[1], front[2], mean,
-                                                                                                   invstd, gamma, a, b)
-                grads[1], grads[2] = dgamma, dbeta
-                g = None
-                break
-            elif (part is not None and l == 0 and ctx.preact and kind == 'sa' and mean.shape[0] <= 1024 and g.is_contiguous()
-                  and z.is_contiguous()):
-                # a hoisted SA level's layer 0: the same for the K = 3 weight gradient (d_wx); dz0 is written (over g) only for the
-                # row scatter of a level with point features
-                idx, rel = front
-                want_term = ctx.has_term and ctx.needs_input_grad[11]
-                sink, loc = _sunk(ctx.f4)
-                dz, front_grads[4], dgamma, dbeta = ops.sa_z0_bnbwd(part, g, z, rel, mean, invstd, gamma, a, b, want_term, dwx_partials=sink is not None)
-                if sink is not None:
-                    sink.push(loc, *front_grads[4])
-                    front_grads[4] = None
-                if want_term:
-                    B, M, ns_ = idx.shape
-                    front_grads[3] = ops.scatter_rows_det(dz.view(B, M * ns_, -1), idx.view(B, M * ns_), ctx.sa_points)
-                grads[1], grads[2] = dgamma, dbeta
-                g = None
-                break
-            elif part is not None:
-                dz, dgamma, dbeta = ops.bn_bwd_from_partials(part, g, z, mean, invstd, gamma, a, b, out=g)   # in place over g
+            hoisted = ctx.preact and l == 0
+            end = None
+            if hoisted and front is not None and group is None and not last and part is not None:
+                end = front.backward_fused(part, g, lay, gamma, front_saved, front_needs)
+            if end is not None:
+                front_grads, dgamma, dbeta = end
             else:
-                dz, dgamma, dbeta = ops.bn_bwd(g, None, z, mean, invstd, gamma, out=g, act_scale=a, act_shift=b)   # in place over g
+                dz, dgamma, dbeta = _bn_backward(lay, gamma, g, (dpooled, arg, ns) if last else None, part, group)
             grads[3 * l + 1], grads[3 * l + 2] = dgamma, dbeta
-            if ctx.preact and l == 0:
-                g = dz                                                                  # d(loss)/d(layer-0 pre-activation)
-                if kind == 'xcorr':
-                    B, n1 = front[0].shape[0], front[0].shape[1]
-                    front_grads[0], front_grads[1], front_grads[2] = ops.xcorr_z0_bwd(dz.contiguous(), front[1], front[2], B, front[1].shape[1], n1)
-                    g = None
-                elif kind == 'sa':
-                    idx, rel = front
-                    B, M, ns_ = idx.shape
-                    dzc = dz.contiguous()
-                    if ctx.has_term and ctx.needs_input_grad[11]:
-                        front_grads[3] = ops.scatter_rows_det(dzc.view(B, M * ns_, -1), idx.view(B, M * ns_), ctx.sa_points)
-                    front_grads[4] = weight_grad(ctx.f4, dzc, rel)
-                    g = None
+            if hoisted:                 # dz = d(loss)/d(layer-0 pre-activation): the caller's rows, or the front's
+                g = dz if front is None else None
+                if front is not None and end is None:
+                    front_grads = front.backward(dz, front_saved, front_needs)
                 break
-            Wp = ctx.weights[l]
-            w2 = Wp.reshape(Wp.shape[0], -1)
-            has_t = in_a.numel() > 0
-            grads[3 * l] = weight_grad(w2, dz, x_in, in_a if has_t else None, in_b if has_t else None)
-            part = None
-            if l > 0:
-                # the gradient w.r.t. the activated input of layer l = the gradient BatchNorm l - 1 receives: its backward sums
-                # come out of this GEMM's epilogue where the persistent row GEMM takes the shape
-                zp, mp, ip, ap, bp = saved[9 * (l - 1) + 3], saved[9 * (l - 1) + 4], saved[9 * (l - 1) + 5], saved[9 * (l - 1) + 6], saved[9 * (l - 1) + 7]
-                if ops.rows_gemm_supported(dz.shape[0], w2.shape[0], w2.shape[1], dz.stride(0), w2.shape[1], x=dz):
-                    g, part = ops.rows_gemm_bnbwd(dz, packed(w2, True), w2.shape[1], zp, mp, ip, ap, bp)
-                else:
-                    g, _ = conv_rows(dz, w2, transpose=True)
-            elif ctx.needs_input_grad[0]:
-                g, _ = conv_rows(dz, w2, transpose=True)                                # w.r.t. the (not normalised) input rows
-            else:
-                g = None
+            grads[3 * l] = weight_grad(w2, dz, lay.x_in, lay.in_a, lay.in_b)
+            g, part = _input_grad(dz, w2, prev) if l > 0 or ctx.needs_input_grad[0] else (None, None)
         for l in range(L):
             if grads[3 * l] is not None:
                 grads[3 * l] = grads[3 * l].view_as(params[3 * l])
             grads[3 * l + 1] = small_grad(ctx.param_objs[3 * l + 1], grads[3 * l + 1])
             grads[3 * l + 2] = small_grad(ctx.param_objs[3 * l + 2], grads[3 * l + 2])
-        return (g, None, None, None, None, None, None, None) + tuple(front_grads) + tuple(grads)
+        return (g, None) + tuple(front_grads) + tuple(grads)
 
 
 def shared_mlp_pool(grouped, mlp, pool_dim):
@@ -699,8 +750,8 @@ def _sync_group(bn):
 def rows_mlp_pool(rows, mlp, ns, B, keep, preact, z0_part=None, front=None, as_rows=False):
     """The row form: rows (B * keep * ns, C) ordered (frame, kept position, pooled position) -> (B, C_L, keep).
     preact: rows are layer 0's convolution output already (hoisted by the caller); z0_part: its BatchNorm statistics as float64
-    partial sums (chunks, 2, C), when the launch that built the rows summed them (ops.sa_z0_rows). front = (meta, tensors) with
-    rows = None: layer 0's rows are built inside the stage's autograd function (_SharedMlpPool.forward, `front`)."""
+    partial sums (chunks, 2, C), when the launch that built the rows summed them. front (an _XcorrFront / _SaFront) with rows = None:
+    layer 0's rows are built from the front's tensors inside the stage's autograd function (_SharedMlpPool.forward)."""
     params, eps, sync = [], [], []
     for unit in mlp:
         bn = unit.normlayer.bn
@@ -708,8 +759,13 @@ def rows_mlp_pool(rows, mlp, ns, B, keep, preact, z0_part=None, front=None, as_r
         eps.append(float(bn.eps))
         sync.append(_sync_group(bn))
     bns = tuple(unit.normlayer.bn if g is None else None for unit, g in zip(mlp, sync))
-    meta, ft = (front[0], tuple(front[1]) + (None,) * (5 - len(front[1]))) if front is not None else (None, (None,) * 5)
-    out = _SharedMlpPool.apply(rows, ns, tuple(eps), bool(preact), tuple(sync), bns, z0_part, meta, *ft, *params)
+    ft = ()
+    if front is not None:
+        # top-level arguments from here on (autograd looks at those only); the function's ctx keeps `front`, which must not keep
+        # its inputs alive
+        ft, front.tensors = front.tensors, None
+    spec = _StageSpec(ns, tuple(eps), bool(preact), tuple(sync), bns, z0_part, front, len(ft))
+    out = _SharedMlpPool.apply(rows, spec, *ft, *params)
     pooled, stats = out[0], out[1:]
     with torch.no_grad():                                   # nn.BatchNorm's bookkeeping in training mode: done by the statistics'
         for l, unit in enumerate(mlp):                      # own launch, except for SyncBatchNorm layers (all-reduced count)
@@ -737,7 +793,7 @@ def sa_level_hoisted(xyz, new_xyz, features, idx, mlp, radius, normalize_xyz):
         # the three coordinate channels — is one launch; features None: a level without point features (layer 0 = Wx . rel)
         term = _RowsLinear.apply(features.transpose(1, 2), wf, None, None) if features is not None else None
         # z0 = term[idx] + Wx . rel is built inside the stage's function (ops.sa_z0_rows): its backward ends with ops.sa_z0_bnbwd
-        return rows_mlp_pool(None, mlp, ns, B, M, preact=True, front=(('sa', float(radius), bool(normalize_xyz)), (xyz, new_xyz, idx, term, wx)))
+        return rows_mlp_pool(None, mlp, ns, B, M, preact=True, front=_SaFront(radius, normalize_xyz, xyz, new_xyz, idx, term, wx))
     rel = pu.grouping_operation(xyz.transpose(1, 2).contiguous(), idx) - new_xyz.transpose(1, 2).unsqueeze(-1)   # (B,3,M,ns)
     if normalize_xyz:
         rel = rel / radius
@@ -763,7 +819,7 @@ def xcorr_hoisted(search_feats, template_feats, template_xyz, mlp, eps):
     P = _RowsLinear.apply(rows_i, wrest, None, None)                                    # (B,n1,C0)
     # z0 (B*n2*n1, C0), rows ordered (b, j, i), is built inside the stage's function: its backward ends with one pass over the
     # gradient of the activated z0 (ops.xcorr_z0_bnbwd)
-    return rows_mlp_pool(None, mlp, n1, B, n2, preact=True, front=(('xcorr',), (P.contiguous(), cos.contiguous(), wsim.reshape(-1).contiguous())))
+    return rows_mlp_pool(None, mlp, n1, B, n2, preact=True, front=_XcorrFront(P.contiguous(), cos.contiguous(), wsim.reshape(-1).contiguous()))
 
 
 class _CosMap(torch.autograd.Function):
@@ -886,8 +942,8 @@ class _AttnCore(torch.autograd.Function):
         q, kf, vf, pos = q.contiguous(), kf.contiguous(), vf.contiguous(), pos.contiguous()
         t = ops.pt_pair_input(q, kf, knn, pos)
         x2 = t.view(-1, t.shape[-1] // heads)
-        h = lin_rows(x2, W1, b1.detach(), relu=True)
-        a = lin_rows(h, W2, b2.detach()).view(*t.shape[:-1], W2.shape[0] * heads)
+        h, a = _mlp2_forward(x2, W1, b1, W2, b2)
+        a = a.view(*t.shape[:-1], W2.shape[0] * heads)
         attn, res = ops.pt_attn_train_fwd(a, vf, knn, pos, scale)
         ctx.save_for_backward(x2, h, attn, vf, knn, pos, order, start, W1, W2)      # the weights too: see _RowsLinear
         ctx.Ws, ctx.bs, ctx.scale, ctx.heads = (W1, W2), (b1, b2), float(scale), int(heads)
@@ -904,17 +960,8 @@ class _AttnCore(torch.autograd.Function):
         da, dvp = ops.pt_attn_train_bwd(attn, vf, knn, pos, dres, ctx.scale)
         dvf = ops.scatter_rows_det(dvp.view(B, N * k, D), knn.view(B, N * k), N, csr)
         heads = ctx.heads
-        dy2 = da.view(-1, D // heads)
-        rows, D1 = h.shape
-        dW2 = weight_grad(W2, dy2, h)
-        db2 = bias_grad(ctx.bs[1], dy2)
-        if ops.rows_gemm_supported(rows, W2.shape[0], D1, dy2.stride(0), D1, x=dy2):
-            dz1, db1 = ops.rows_gemm_masked(dy2, packed(W2, True), D1, h, want_colsum=True)
-        else:
-            dz1 = lin_rows(dy2, W2, transpose=True) * (h > 0)
-            db1 = dz1.sum(0)
-        dW1 = weight_grad(W1, dz1, x2)
-        Din = W1.shape[1]
+        dz1, dW1, db1, dW2, db2 = _mlp2_backward(da.view(-1, D // heads), x2, h, W1, ctx.bs[0], W2, ctx.bs[1])
+        D1, Din = W1.shape
         if heads == 1 and ops.rows_gemm_rsum16_supported(dz1, D1, Din) and k == 16 and Din == D:
             dt, dpos, dq = ops.rows_gemm_rsum16(dz1, packed(W1, True), Din, dvp.view(-1, D))
             dkf = ops.scatter_rows_det(dt.view(B, N * k, D), knn.view(B, N * k), N, csr, negate=True)
@@ -928,7 +975,7 @@ class _AttnCore(torch.autograd.Function):
             dq = dt.sum(dim=2)
             dkf = ops.scatter_rows_det(dt.view(B, N * k, D), knn.view(B, N * k), N, csr).neg_()
             dpos = dt + dvp
-        return dq, dkf, dvf, None, dpos, dW1, small_grad(ctx.bs[0], db1), dW2, db2, None, None, None, None
+        return dq, dkf, dvf, None, dpos, dW1, db1, dW2, db2, None, None, None, None
 
 
 def attn_core(fc_gamma, q, kf, vf, knn, pos, scale, order, start, heads=1):
@@ -993,6 +1040,29 @@ def lin_rows(x2, W, b=None, relu=False, residual=None, transpose=False):
     return ops.linear(x2, wp, cout, None, b, relu, residual)
 
 
+def _mlp2_forward(x2, W1, b1, W2, b2):
+    """-> (h, y) = (relu(x2 W1^T + b1), h W2^T + b2): bias and ReLU in the first GEMM's epilogue."""
+    h = lin_rows(x2, W1, b1.detach(), relu=True)
+    return h, lin_rows(h, W2, b2.detach())
+
+
+def _mlp2_backward(dy2, x2, h, W1, b1, W2, b2):
+    """The backward pass of _mlp2_forward up to the first layer's pre-activation -> (dz1, dW1, db1, dW2, db2); the input gradient
+    dz1 W1 is the caller's. dz1 comes out of the second layer's input-gradient GEMM already masked by the ReLU, together with its
+    column sums (= db1) — ptt_rows_gemm_masked_f32. The parameter gradients are finished tensors, or None once a GradSink has them
+    (handed over in the order W2, b2, W1, b1)."""
+    rows, D1 = h.shape
+    dW2 = weight_grad(W2, dy2, h)
+    db2 = bias_grad(b2, dy2)
+    if ops.rows_gemm_supported(rows, W2.shape[0], D1, dy2.stride(0), D1, x=dy2):
+        dz1, db1 = ops.rows_gemm_masked(dy2, packed(W2, True), D1, h, want_colsum=True)
+    else:
+        dz1 = lin_rows(dy2, W2, transpose=True) * (h > 0)
+        db1 = dz1.sum(0)
+    dW1 = weight_grad(W1, dz1, x2)
+    return dz1, dW1, small_grad(b1, db1), dW2, db2
+
+
 class _RowsLinear(torch.autograd.Function):
     """y = x W^T + b (+ residual) over (rows, K) on the hand-written kernels: forward and input gradient on the row GEMM /
     linear kernel, weight gradient on ptt_linear_wgrad(2)_f32, bias gradient = column sums. Every nn.Linear of the
@@ -1037,8 +1107,7 @@ class _RowsMlp2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        h = lin_rows(x2, W1, b1.detach(), relu=True)
-        y = lin_rows(h, W2, b2.detach())
+        h, y = _mlp2_forward(x2, W1, b1, W2, b2)
         ctx.save_for_backward(x2, h, W1, W2)                 # the weights too: see _RowsLinear
         ctx.Ws, ctx.bs = (W1, W2), (b1, b2)
         ctx.shape = x.shape
@@ -1048,18 +1117,9 @@ class _RowsMlp2(torch.autograd.Function):
     def backward(ctx, dy):
         x2, h, _, _ = ctx.saved_tensors
         W1, W2 = ctx.Ws
-        dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        rows, D1 = h.shape
-        dW2 = weight_grad(W2, dy2, h)
-        db2 = bias_grad(ctx.bs[1], dy2)
-        if ops.rows_gemm_supported(rows, W2.shape[0], D1, dy2.stride(0), D1, x=dy2):
-            dz1, db1 = ops.rows_gemm_masked(dy2, packed(W2, True), D1, h, want_colsum=True)
-        else:
-            dz1 = lin_rows(dy2, W2, transpose=True) * (h > 0)
-            db1 = dz1.sum(0)
-        dW1 = weight_grad(W1, dz1, x2)
+        dz1, dW1, db1, dW2, db2 = _mlp2_backward(dy.reshape(-1, dy.shape[-1]).contiguous(), x2, h, W1, ctx.bs[0], W2, ctx.bs[1])
         dx = lin_rows(dz1, W1, transpose=True).view(ctx.shape) if ctx.needs_input_grad[0] else None
-        return dx, dW1, small_grad(ctx.bs[0], db1), dW2, db2
+        return dx, dW1, db1, dW2, db2
 
 
 def rows_mlp2(seq, x):
@@ -1074,19 +1134,11 @@ def conv1d_stack_usable(seq, x):
         return False
     units = list(seq)
     for k, unit in enumerate(units):
-        conv = getattr(unit, 'conv', None)
-        if not isinstance(conv, nn.Conv1d) or conv.kernel_size != (1,) or conv.stride != (1,) or conv.padding != (0,) or conv.groups != 1:
-            return False
         if hasattr(unit, 'normlayer'):
-            bn = getattr(unit.normlayer, 'bn', None)
-            if (not isinstance(bn, (nn.BatchNorm1d, nn.SyncBatchNorm)) or not bn.affine or not bn.track_running_stats
-                    or bn.momentum is None or not bn.training or conv.bias is not None or conv.weight.shape[0] % 4):
+            if not _conv_bn_relu_unit(unit, nn.Conv1d, nn.BatchNorm1d, (1,), x.device):
                 return False
-            if not isinstance(getattr(unit, 'activation', None), nn.ReLU) or list(unit._modules.keys()) != ['conv', 'normlayer', 'activation']:
-                return False
-            if not _raw_pointer_ready(conv, bn, x.device):
-                return False
-        elif k != len(units) - 1 or list(unit._modules.keys()) != ['conv'] or not _raw_pointer_ready(conv, None, x.device):
+        elif (k != len(units) - 1 or list(unit._modules.keys()) != ['conv'] or not _pointwise_conv(unit.conv, nn.Conv1d, (1,))
+              or not _raw_pointer_ready(unit.conv, None, x.device)):
             return False
     return True
 
