@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 26
+#define PTT_ABI_VERSION 27
 
 enum {
     PTT_OK = 0,
@@ -540,6 +540,26 @@ int ptt_track_select_update(const float* proposals_host, int P, const int32_t* i
  * pred_box_data (B,P,5) with the largest score (column 4; first one among equals, as np.argmax) -> out (B,5);
  * idx_out (B) receives its index, or NULL. */
 int ptt_select_box_f32(const float* pred_box_data, int B, int P, float* out, int32_t* idx_out, ptt_stream_t stream);
+
+/* ptt_box_overlap_f64 (ABI 27) — the two numbers the reference scores a tracked frame by (tools/eval_utils/
+ * eval_tracking_metrics.py:37-74), for n (ground truth, result) box pairs in one launch, one pair per thread, all in float64:
+ *   overlap[i]  = estimateOverlap(gt[i], pred[i], dims, ref_coord)     accuracy[i] = estimateAccuracy(gt[i], pred[i], dims)
+ * gt / pred: n boxes in the ptt_track_box layout (centre 3, wlh 3, quaternion w x y z), DEVICE memory.
+ *   equality   overlap = 1.0 exactly when every one of the 10 numbers has |gt - pred| <= 1e-8 + 1e-5 * |pred|: Box.__eq__
+ *              (kitti_tracking_utils.py:84-93), i.e. np.allclose(gt, pred), asymmetric as numpy's is;
+ *   footprint  four of Box.corners (:132-150; the quaternion is general, not only a yaw): PTT_REF_CAMERA corners 0, 1, 5, 4 on
+ *              (x, z), PTT_REF_LIDAR corners 2, 3, 7, 6 (bottom_corners) on (x, y); each quadrilateral is put in
+ *              counter-clockwise order by its signed area, gt's is clipped by the four half-planes of pred's (Sutherland-Hodgman,
+ *              at most 8 vertices), the area is the shoelace sum, fewer than 3 vertices = 0;
+ *   dims == 2  inter / (area_gt + area_pred - inter), the areas those of the two footprints;
+ *   dims == 3  inter * max(0, ymax - ymin) / (vol_gt + vol_pred - that), vol = w * l * h, ymax = min(centre_y), ymin =
+ *              max(centre_y - h) — formed from component 1 of the centres under BOTH conventions, as the reference does (:65-67);
+ *   accuracy   |centre_gt - centre_pred|, dims == 2: over components 0 and 2 (:41-42).
+ * Boxes with a non-positive size are outside the contract. Another dims or ref_coord: PTT_EINVAL; n == 0 launches nothing. */
+#define PTT_REF_CAMERA 0
+#define PTT_REF_LIDAR 1
+int ptt_box_overlap_f64(const double* gt, const double* pred, int n, int ref_coord, int dims, double* overlap, double* accuracy,
+                        ptt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * N3  training step of the shared-MLP stages on hand-written kernels. The reference's SharedMLP in train mode is

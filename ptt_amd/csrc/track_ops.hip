@@ -10,6 +10,8 @@
 //                        cloud; n == size is copied through. Template clouds are the concatenation of several crops
 //                        (get_model, :219-236).
 //   select_box_kernel    post_process (:266-274): first arg-max of the proposal scores, its 4-dof offset and score.
+//   box_overlap_kernel   estimateOverlap / estimateAccuracy (tools/eval_utils/eval_tracking_metrics.py:37-74) of every (ground truth,
+//                        result) pair of an evaluation in one launch, float64: what Success / Precision are computed from.
 // Arithmetic follows numpy's: points are float32, box quantities float64; `translate` rounds (double)p + t to float32,
 // `rotate` rounds the float64 dot product to float32; comparisons are float32 point against float64 bound, strict.
 #include <math.h>
@@ -238,6 +240,136 @@ __global__ __launch_bounds__(256) void select_box_kernel(const float* __restrict
     if (lane == 0 && idx_out) idx_out[b] = win;
 }
 
+// ---- box_overlap_kernel: Success / Precision inputs (tools/eval_utils/eval_tracking_metrics.py:37-74), one pair per thread ----
+// A polygon of the clip: at most 8 vertices (a quadrilateral gains at most one per half-plane). The vertices live in REGISTERS:
+// every loop over them is fully unrolled and every element access has a compile-time index — reading vertex j + 1 and appending
+// at the running count are selects over the 8 slots (poly_put) — so the compiler keeps x[] / y[] in vector registers and the
+// kernel has no private (scratch) segment. The alternative, `out[m++] = v` with a run-time m, is shorter by a few lines and
+// sends both buffers to scratch memory.
+struct Poly8 {
+    double x[8], y[8];
+    int n;
+};
+
+// v -> slot m (dropped when m >= 8: only rounding noise on an edge that lies ALONG a clip line can ask for a ninth vertex, and
+// such a vertex repeats one that is already there)
+__device__ __forceinline__ void poly_put(Poly8& p, int m, double vx, double vy) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k == m) { p.x[k] = vx; p.y[k] = vy; }
+}
+
+// 0.5 * sum_i (x_i y_{i+1} - x_{i+1} y_i) over the first n vertices, summed in vertex order
+__device__ __forceinline__ double poly_area(const Poly8& p) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (k < p.n) {
+            const bool last = (k + 1 == p.n) || (k == 7);
+            const double nx = last ? p.x[0] : p.x[(k + 1) & 7], ny = last ? p.y[0] : p.y[(k + 1) & 7];
+            s += p.x[k] * ny - nx * p.y[k];
+        }
+    }
+    return 0.5 * s;
+}
+
+// Box.corners (kitti_tracking_utils.py:132-150) restricted to the footprint: camera = corners 0, 1, 5, 4 on (x, z), lidar =
+// corners 2, 3, 7, 6 (bottom_corners) on (x, y); then counter-clockwise by the signed area. Returns |area|.
+__device__ __forceinline__ double footprint(const double* __restrict__ b, int ref_coord, double (&fx)[4], double (&fy)[4]) {
+    // Quaternion.rotation_matrix: normalised unless already unit to 1e-14 (pyquaternion's _fast_normalise test), as q_rotation_matrix below
+    double w = b[6], x = b[7], y = b[8], z = b[9];
+    const double nq = sqrt(w * w + x * x + y * y + z * z);
+    if (!(fabs(1.0 - nq * nq) < 1e-14) && nq > 0) { w /= nq; x /= nq; y /= nq; z /= nq; }
+    // rows 0 and (camera: 2, lidar: 1) of the matrix
+    const double r00 = x * x + w * w - z * z - y * y, r01 = x * y - w * z - z * w + y * x, r02 = x * z + w * y + z * x + y * w;
+    const bool cam = ref_coord == PTT_REF_CAMERA;
+    const double s0 = cam ? z * x - y * w + x * z - w * y : y * x + z * w + w * z + x * y;
+    const double s1 = cam ? z * y + y * z + x * w + w * x : y * y - z * z + w * w - x * x;
+    const double s2 = cam ? z * z - y * y - x * x + w * w : y * z + z * y - w * x - x * w;
+    const double c0 = b[0], c1 = cam ? b[2] : b[1];
+    const double hl = b[4] / 2, hw = b[3] / 2, hh = b[5] / 2;
+    // box-frame signs of the four corners: x (length) +, +, -, - for both conventions; y (width) +, -, -, + (camera: corners
+    // 0 1 5 4) or -, +, +, - (lidar: 2 3 7 6); z (height) + (camera) or - (lidar)
+    const double ly0 = cam ? hw : -hw, lz = cam ? hh : -hh;
+    const double lx[4] = {hl, hl, -hl, -hl}, ly[4] = {ly0, -ly0, -ly0, ly0};
+    double px[4], py[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        px[k] = (r00 * lx[k] + r01 * ly[k] + r02 * lz) + c0;
+        py[k] = (s0 * lx[k] + s1 * ly[k] + s2 * lz) + c1;
+    }
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a += px[k] * py[(k + 1) & 3] - px[(k + 1) & 3] * py[k];
+    a *= 0.5;
+    const bool flip = a < 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { fx[k] = flip ? px[3 - k] : px[k]; fy[k] = flip ? py[3 - k] : py[k]; }
+    return fabs(a);
+}
+
+__global__ __launch_bounds__(256) void box_overlap_kernel(const double* __restrict__ gt, const double* __restrict__ pred, int n, int ref_coord,
+                                                          int dims, double* __restrict__ overlap, double* __restrict__ accuracy) {
+    const int i = blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= n) return;
+    const double* a = gt + (size_t)i * 10;
+    const double* b = pred + (size_t)i * 10;
+    // estimateAccuracy (:37-42)
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    accuracy[i] = dims == 3 ? sqrt(dx * dx + dy * dy + dz * dz) : sqrt(dx * dx + dz * dz);
+    // `if box_a == box_b: return 1.0` (:53-54): np.allclose(gt, pred) over centre, wlh and quaternion elements
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) same = same && (fabs(a[k] - b[k]) <= 1e-8 + 1e-5 * fabs(b[k]));
+    if (same) { overlap[i] = 1.0; return; }
+
+    double ax[4], ay[4], bx[4], by[4];
+    const double area_a = footprint(a, ref_coord, ax, ay);
+    const double area_b = footprint(b, ref_coord, bx, by);
+    // Sutherland-Hodgman: gt's footprint through the four half-planes of pred's (both counter-clockwise: inside = left of the edge)
+    Poly8 cur;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { cur.x[k] = k < 4 ? ax[k] : 0.0; cur.y[k] = k < 4 ? ay[k] : 0.0; }
+    cur.n = 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const double ex = bx[(e + 1) & 3] - bx[e], ey = by[(e + 1) & 3] - by[e];
+        Poly8 out;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { out.x[k] = 0.0; out.y[k] = 0.0; }
+        int m = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < cur.n) {
+                const bool last = (j + 1 == cur.n) || (j == 7);
+                const double p0 = cur.x[j], p1 = cur.y[j];
+                const double q0 = last ? cur.x[0] : cur.x[(j + 1) & 7], q1 = last ? cur.y[0] : cur.y[(j + 1) & 7];
+                const double sp = ex * (p1 - by[e]) - ey * (p0 - bx[e]);
+                const double sq = ex * (q1 - by[e]) - ey * (q0 - bx[e]);
+                if (sp >= 0) { poly_put(out, m, p0, p1); ++m; }
+                if ((sp >= 0) != (sq >= 0)) {
+                    const double t = sp / (sp - sq);
+                    poly_put(out, m, p0 + t * (q0 - p0), p1 + t * (q1 - p1));
+                    ++m;
+                }
+            }
+        }
+        out.n = m < 8 ? m : 8;
+        cur = out;
+    }
+    const double inter = cur.n >= 3 ? fabs(poly_area(cur)) : 0.0;
+    if (dims == 2) {
+        overlap[i] = inter / (area_a + area_b - inter);
+    } else {
+        // the height terms exactly as the reference forms them (:65-73), under both conventions
+        const double ymax = fmin(a[1], b[1]);
+        const double ymin = fmax(a[1] - a[5], b[1] - b[5]);
+        const double inter_vol = inter * fmax(0.0, ymax - ymin);
+        const double vol_a = a[3] * a[4] * a[5], vol_b = b[3] * b[4] * b[5];
+        overlap[i] = inter_vol / (vol_a + vol_b - inter_vol);
+    }
+}
+
 }  // namespace ptt
 
 using namespace ptt;
@@ -444,6 +576,16 @@ extern "C" int ptt_select_box_f32(const float* pred_box_data, int B, int P, floa
     if (!pred_box_data || !out) return fail(PTT_EINVAL, "ptt_select_box_f32: null pointer");
     hipLaunchKernelGGL(select_box_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), pred_box_data, B, P, out, idx_out);
     return check_launch("select_box_kernel");
+}
+
+extern "C" int ptt_box_overlap_f64(const double* gt, const double* pred, int n, int ref_coord, int dims, double* overlap, double* accuracy,
+                                   ptt_stream_t stream) {
+    if (n < 0 || (dims != 2 && dims != 3) || (ref_coord != PTT_REF_CAMERA && ref_coord != PTT_REF_LIDAR))
+        return fail(PTT_EINVAL, "ptt_box_overlap_f64: n=%d ref_coord=%d (0 camera, 1 lidar) dims=%d (2 or 3)", n, ref_coord, dims);
+    if (n == 0) return PTT_OK;
+    if (!gt || !pred || !overlap || !accuracy) return fail(PTT_EINVAL, "ptt_box_overlap_f64: null pointer");
+    hipLaunchKernelGGL(box_overlap_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), gt, pred, n, ref_coord, dims, overlap, accuracy);
+    return check_launch("box_overlap_kernel");
 }
 
 // The host side of post_process for one step of B tracklets in ONE call (eval_tracking_utils.py:266-274 + the generator bookkeeping

@@ -772,6 +772,31 @@ def select_box(pred_box_data, out=None, idx_out=None):
     return out
 
 
+REF_COORDS = {"camera": _lib.DEFINES["PTT_REF_CAMERA"], "lidar": _lib.DEFINES["PTT_REF_LIDAR"]}
+
+
+def box_overlap(gt, pred, ref_coord, dims=3, out=None):
+    """(n,10), (n,10) f64 -> overlap (n,), accuracy (n,) f64: estimateOverlap / estimateAccuracy of the reference's evaluation
+    (tools/eval_utils/eval_tracking_metrics.py:37-74) for every (ground truth, result) pair in one launch. A box row is centre 3,
+    wlh 3, quaternion (w, x, y, z) — the ptt_track_box layout; ref_coord 'camera' / 'lidar' (any case, as the reference reads its
+    REF_COOR setting) or the PTT_REF_* value. out: a (2,n) f64 buffer for the two results (one read-back), else allocated."""
+    _chk(gt, "gt", torch.float64, 2)
+    _chk(pred, "pred", torch.float64, 2)
+    n = gt.shape[0]
+    if gt.shape[1] != 10 or tuple(pred.shape) != (n, 10) or pred.device != gt.device:
+        raise RuntimeError("gt and pred must be (n,10) on one device, got %s and %s" % (tuple(gt.shape), tuple(pred.shape)))
+    if isinstance(ref_coord, str):
+        if ref_coord.lower() not in REF_COORDS:
+            raise ValueError("ref_coord must be 'camera' or 'lidar', got %r" % (ref_coord,))
+        ref_coord = REF_COORDS[ref_coord.lower()]
+    if out is None:
+        out = torch.empty((2, n), dtype=torch.float64, device=gt.device)
+    elif _chk(out, "out", torch.float64, 2).shape != (2, n) or out.device != gt.device:
+        raise RuntimeError("out must be (2,%d) on the boxes' device, got %s" % (n, tuple(out.shape)))
+    _launch("ptt_box_overlap_f64", gt.device, _ptr(gt), _ptr(pred), n, int(ref_coord), int(dims), _ptr(out[0]), _ptr(out[1]))
+    return out[0], out[1]
+
+
 # --------------------------------------------------------------------------- N3: training-step kernels (rows x channels)
 WGRAD2 = os.environ.get("PTT_WGRAD2", "1") != "0"        # dev A/B: the round-2 128 x 128-block weight-gradient kernel
 
