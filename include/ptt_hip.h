@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 27
+#define PTT_ABI_VERSION 28
 
 enum {
     PTT_OK = 0,
@@ -560,6 +560,73 @@ int ptt_select_box_f32(const float* pred_box_data, int B, int P, float* out, int
 #define PTT_REF_LIDAR 1
 int ptt_box_overlap_f64(const double* gt, const double* pred, int n, int ref_coord, int dims, double* overlap, double* accuracy,
                         ptt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * N5 (ABI 28)  device-resident training batches: the reference's get_train_items (ptt/datasets/kitti/
+ * kitti_dataset_tracking.py:60-179), batched. A batch of B samples is drawn from B + spare CANDIDATES (B primaries, then the
+ * spares that stand in for rejected primaries) in two launches, with no count ever crossing PCIe:
+ *   launch 1  ptt_crop_compact_f32 over 3 jobs per candidate: the search crop with labels (prepare_search_and_label :120-138),
+ *             the first-frame and the previous-frame template crop (get_model, prepare_template_data :151-174) into per-candidate
+ *             scratch sized for the largest resident cloud; the three counts stay on the device;
+ *   launch 2  ptt_train_batch_f32, one workgroup per output slot b < B:
+ *     validity    candidate c is valid when n_search > min_points and n_first + n_prev > min_points (:140, :176: a crop of
+ *                 <= 20 points rejects the sample);
+ *     source      a valid primary b is its own source. An invalid one takes the r-th valid spare, r = the number of invalid
+ *                 primaries before b (the reference retries a uniformly random index, :76,:99: the spares are such indices, drawn
+ *                 by the host). With fewer valid spares than that (a SHORTFALL) it takes valid candidate number
+ *                 (r - n_valid_spares) mod n_valid, counted over primaries then spares; with no valid candidate at all the slot is
+ *                 all zeros and its source -1;
+ *     resampling  regularize_pc(istrain=True) (kitti_tracking_utils.py:342-367): n == size -> the rows in order; otherwise row i
+ *                 of the output is row idx_i of the crop, idx_i = (uint64(w_i) * n) >> 32 with w_i = word i & 3 of
+ *                 Philox4x32-10(counter = (i >> 2, index, which, epoch), key = (seed_lo, seed_hi)), which = 0 search, 1 template
+ *                 (Salmon et al., SC'11; bias n / 2^32, no rejection, no generator state: the reference's np.random.randint draws
+ *                 from numpy's per-worker global generator, which no device can follow). The search labels ride on the same
+ *                 indices (:354-355) and come out as float32 0 / 1; the template is resampled over first || previous;
+ *     reg_label   the candidate's four float32 values (formed in float64 by the host, :324); src_out[b] = the source candidate;
+ *     idx_*_out   (may be NULL) the drawn indices, -1 throughout for a pass-through or an all-zero slot;
+ *     info        (may be NULL) 4 x int32 written by slot 0's workgroup: invalid primaries, valid spares, shortfall =
+ *                 max(0, invalid primaries - valid spares), all_invalid (0 / 1); totals (may be NULL) 4 x int64 raised by the same
+ *                 thread: batches, then the running sums of the first three of those. Batches that share `totals` must run on one stream.
+ * The candidate table lives in DEVICE memory; the descriptor is HOST memory, read before the call returns (passed by value with
+ * the launch). The outputs need only their element alignment: rows are written as float4 / int4 where the size is a multiple
+ * of four and the base pointers are 16-byte aligned, element by element otherwise. Every address is fixed by the tables, so both launches replay from a hipGraph. 1 <= B <= n_cand <=
+ * PTT_TRAIN_MAX_CANDS, sizes >= 1, min_points >= 2; anything else: PTT_EINVAL.
+ * ------------------------------------------------------------------------------- */
+#define PTT_TRAIN_MAX_CANDS 1024
+typedef struct ptt_train_cand {
+    const float* search;        /* (capacity, 3) the search crop, (capacity) its labels: a label job's out / label_out */
+    const uint8_t* label;
+    const float* first;         /* (capacity, 3) the template's two crops */
+    const float* prev;
+    const int32_t* counts;      /* 3 device scalars: rows of search, first, prev (the crop jobs' counts; clamped to capacity) */
+    float reg[4];               /* reg_label */
+    uint32_t index;             /* the dataset index: word 1 of the Philox counter */
+    uint32_t epoch;             /* word 3 */
+    int32_t capacity;
+    int32_t reserved;           /* 0 */
+} ptt_train_cand;
+
+typedef struct ptt_train_batch_desc {
+    float* search_points;       /* (B, search_size, 3) */
+    float* template_points;     /* (B, template_size, 3) */
+    float* cls_label;           /* (B, search_size) */
+    float* reg_label;           /* (B, 4) */
+    int32_t* src_out;           /* (B) */
+    int32_t* idx_search_out;    /* (B, search_size) or NULL */
+    int32_t* idx_template_out;  /* (B, template_size) or NULL */
+    int32_t* info;              /* (4) or NULL */
+    int64_t* totals;            /* (4) or NULL */
+    int32_t B, n_cand;
+    int32_t search_size, template_size;
+    int32_t min_points;
+    uint32_t seed_lo, seed_hi;  /* the Philox key */
+    int32_t reserved;           /* 0 */
+} ptt_train_batch_desc;
+
+int ptt_train_batch_f32(const ptt_train_cand* cands_device, const ptt_train_batch_desc* desc_host, ptt_stream_t stream);
+/* The generator of the resampling on the host (HOST pointers, no device work), for tests and tools: out4[0..3] =
+ * Philox4x32-10(counter4, key2). */
+int ptt_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
 
 /* ---------------------------------------------------------------------------------
  * N3  training step of the shared-MLP stages on hand-written kernels. The reference's SharedMLP in train mode is

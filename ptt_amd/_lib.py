@@ -78,6 +78,7 @@ ABI_VERSION = DEFINES["PTT_ABI_VERSION"]
 PTT_SA_MAX_LAYERS = DEFINES["PTT_SA_MAX_LAYERS"]
 PTT_MAX_SEGMENTS = DEFINES["PTT_MAX_SEGMENTS"]
 PTT_CROP_JOBS_BY_VALUE_MAX = DEFINES["PTT_CROP_JOBS_BY_VALUE_MAX"]
+PTT_TRAIN_MAX_CANDS = DEFINES["PTT_TRAIN_MAX_CANDS"]
 
 
 class CropJob(Structure):
@@ -100,6 +101,21 @@ class RegularizeJob(Structure):
 class TrackBox(Structure):
     """ptt_track_box: one tracklet's box in float64, quaternion (w, x, y, z); host memory."""
     _fields_ = [("center", c_double * 3), ("wlh", c_double * 3), ("quat", c_double * 4)]
+
+
+class TrainCand(Structure):
+    """ptt_train_cand: one candidate sample of a training batch (its crops' scratch, labels' values and Philox counter words);
+    arrays of these are uploaded to the device."""
+    _fields_ = [("search", c_void_p), ("label", c_void_p), ("first", c_void_p), ("prev", c_void_p), ("counts", c_void_p),
+                ("reg", c_float * 4), ("index", c_uint32), ("epoch", c_uint32), ("capacity", c_int32), ("reserved", c_int32)]
+
+
+class TrainBatchDesc(Structure):
+    """ptt_train_batch_desc: the outputs and sizes of ptt_train_batch_f32 (passed by value, host memory)."""
+    _fields_ = [("search_points", c_void_p), ("template_points", c_void_p), ("cls_label", c_void_p), ("reg_label", c_void_p),
+                ("src_out", c_void_p), ("idx_search_out", c_void_p), ("idx_template_out", c_void_p), ("info", c_void_p), ("totals", c_void_p),
+                ("B", c_int32), ("n_cand", c_int32), ("search_size", c_int32), ("template_size", c_int32), ("min_points", c_int32),
+                ("seed_lo", c_uint32), ("seed_hi", c_uint32), ("reserved", c_int32)]
 
 
 class BnTrainTail(Structure):

@@ -12,6 +12,9 @@
 //   select_box_kernel    post_process (:266-274): first arg-max of the proposal scores, its 4-dof offset and score.
 //   box_overlap_kernel   estimateOverlap / estimateAccuracy (tools/eval_utils/eval_tracking_metrics.py:37-74) of every (ground truth,
 //                        result) pair of an evaluation in one launch, float64: what Success / Precision are computed from.
+//   train_batch_kernel   N5: a training batch out of the crops of B + spare candidates (get_train_items, ptt/datasets/kitti/
+//                        kitti_dataset_tracking.py:60-179): validity, replacement of rejected samples by spares, and regularize_pc(istrain=
+//                        True) of search (+ labels) and template on counter-based Philox4x32-10 indices.
 // Arithmetic follows numpy's: points are float32, box quantities float64; `translate` rounds (double)p + t to float32,
 // `rotate` rounds the float64 dot product to float32; comparisons are float32 point against float64 bound, strict.
 #include <math.h>
@@ -370,6 +373,137 @@ __global__ __launch_bounds__(256) void box_overlap_kernel(const double* __restri
     }
 }
 
+// ---- train_batch_kernel (N5): one workgroup per output slot of a training batch ----
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of two 32 x 32 -> 64
+// multiplications, the key raised by the Weyl constants between rounds.
+__host__ __device__ __forceinline__ void philox4x32_10(const uint32_t (&ctr)[4], uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Rows i = 4t .. 4t + 3 of one output cloud (thread-owned: one Philox block): row idx of seg0 (n0 rows) || seg1, optionally
+// the label of that row as float32, optionally the index. n == size passes the rows through in order (index -1); n == 0 (an
+// all-invalid batch) writes zeros. `vec`: size % 4 == 0 and 16-byte aligned outputs, so the 12 floats of the four rows are three
+// aligned float4 stores; otherwise element by element.
+__device__ __forceinline__ void resample_rows(bool vec, int t, int size, int n, int n0, const float* __restrict__ seg0, const float* __restrict__ seg1,
+                                              const uint8_t* __restrict__ label, uint32_t index, uint32_t which, uint32_t epoch, uint32_t k0,
+                                              uint32_t k1, float* __restrict__ out, float* __restrict__ label_out, int32_t* __restrict__ idx_out) {
+    const uint32_t ctr[4] = {(uint32_t)t, index, which, epoch};
+    uint32_t w[4] = {0, 0, 0, 0};
+    const bool draw = n > 0 && n != size;
+    if (draw) philox4x32_10(ctr, k0, k1, w);
+    float v[12], lab[4];
+    int32_t id[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = 4 * t + k;
+        int src = draw ? (int)(((uint64_t)w[k] * (uint64_t)(uint32_t)n) >> 32) : i;
+        id[k] = draw ? src : -1;
+        v[3 * k] = v[3 * k + 1] = v[3 * k + 2] = 0.f;
+        lab[k] = 0.f;
+        if (i < size && n > 0) {                   // src < n always: a drawn index by construction, a pass-through one since i < size == n
+            const float* p = src < n0 ? seg0 + (size_t)src * 3 : seg1 + (size_t)(src - n0) * 3;
+            v[3 * k] = p[0]; v[3 * k + 1] = p[1]; v[3 * k + 2] = p[2];
+            if (label) lab[k] = label[src] ? 1.f : 0.f;
+        }
+    }
+    const int i0 = 4 * t;
+    if (vec) {
+        float4* o = reinterpret_cast<float4*>(out + (size_t)i0 * 3);
+        o[0] = make_float4(v[0], v[1], v[2], v[3]);
+        o[1] = make_float4(v[4], v[5], v[6], v[7]);
+        o[2] = make_float4(v[8], v[9], v[10], v[11]);
+        if (label_out) *reinterpret_cast<float4*>(label_out + i0) = make_float4(lab[0], lab[1], lab[2], lab[3]);
+        if (idx_out) *reinterpret_cast<int4*>(idx_out + i0) = make_int4(id[0], id[1], id[2], id[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i0 + k < size) {
+                out[(size_t)(i0 + k) * 3] = v[3 * k]; out[(size_t)(i0 + k) * 3 + 1] = v[3 * k + 1]; out[(size_t)(i0 + k) * 3 + 2] = v[3 * k + 2];
+                if (label_out) label_out[i0 + k] = lab[k];
+                if (idx_out) idx_out[i0 + k] = id[k];
+            }
+        }
+    }
+}
+
+template <int T>
+__global__ __launch_bounds__(T) void train_batch_kernel(const ptt_train_cand* __restrict__ cands, const ptt_train_batch_desc D) {
+    __shared__ int wsum[T / 64];
+    __shared__ int vrank[PTT_TRAIN_MAX_CANDS + 1];          // valid candidates before c; [n_cand] = their total
+    __shared__ unsigned char vflag[PTT_TRAIN_MAX_CANDS];
+    __shared__ int source;
+    const int b = blockIdx.x, B = D.B, C = D.n_cand;
+    // validity of every candidate and its rank among the valid ones (C <= PTT_TRAIN_MAX_CANDS: at most 4 chunks)
+    int seen = 0;
+    for (int base = 0; base < C; base += T) {
+        const int c = base + (int)threadIdx.x;
+        bool ok = false;
+        if (c < C) {
+            const int32_t* cnt = cands[c].counts;
+            const int cap = cands[c].capacity;
+            const int ns = min(cnt[0], cap), n1 = min(cnt[1], cap), n2 = min(cnt[2], cap);
+            ok = ns > D.min_points && n1 + n2 > D.min_points;
+        }
+        int total;
+        const int r = seen + block_rank<T>(ok, wsum, total);
+        if (c < C) { vrank[c] = r; vflag[c] = ok ? 1 : 0; }
+        seen += total;
+    }
+    if (threadIdx.x == 0) { vrank[C] = seen; source = -1; }
+    __syncthreads();
+    const int n_valid = seen, valid_prim = vrank[B], valid_spare = n_valid - valid_prim, invalid_prim = B - valid_prim;
+    // the rank, among the valid candidates, of the one this slot takes
+    int want = -1;
+    if (vflag[b]) want = vrank[b];
+    else if (n_valid > 0) {
+        const int r = b - vrank[b];                           // invalid primaries before b
+        want = r < valid_spare ? valid_prim + r : (r - valid_spare) % n_valid;
+    }
+    for (int c = threadIdx.x; c < C; c += T)
+        if (vflag[c] && vrank[c] == want) source = c;         // exactly one candidate has that rank
+    __syncthreads();
+    const int src = source;
+    if (b == 0 && threadIdx.x == 0) {
+        const int shortfall = max(0, invalid_prim - valid_spare);
+        if (D.info) { D.info[0] = invalid_prim; D.info[1] = valid_spare; D.info[2] = shortfall; D.info[3] = n_valid == 0; }
+        // one thread of one workgroup, and the batches that share `totals` run in stream order: plain read-modify-write
+        if (D.totals) { D.totals[0] += 1; D.totals[1] += invalid_prim; D.totals[2] += shortfall; D.totals[3] += n_valid == 0; }
+    }
+    int ns = 0, n1 = 0, n2 = 0;
+    uint32_t index = 0, epoch = 0;
+    const float *ps = nullptr, *p1 = nullptr, *p2 = nullptr;
+    const uint8_t* pl = nullptr;
+    float reg = 0.f;
+    if (src >= 0) {
+        const ptt_train_cand& c = cands[src];
+        const int cap = c.capacity;
+        ns = min(c.counts[0], cap); n1 = min(c.counts[1], cap); n2 = min(c.counts[2], cap);
+        ps = c.search; pl = c.label; p1 = c.first; p2 = c.prev; index = c.index; epoch = c.epoch;
+        if (threadIdx.x < 4) reg = c.reg[threadIdx.x];
+    }
+    if (threadIdx.x < 4) D.reg_label[(size_t)b * 4 + threadIdx.x] = reg;
+    if (threadIdx.x == 0) D.src_out[b] = src;
+    const int S = D.search_size, Tn = D.template_size;
+    // the float4 stores need rows that start on 16 bytes: a size that is a multiple of four on a 16-byte aligned base (NULL is)
+    const auto misaligned = [](const void* p) { return ((uintptr_t)p & 15u) != 0; };
+    const bool vec_s = (S & 3) == 0 && !misaligned(D.search_points) && !misaligned(D.cls_label) && !misaligned(D.idx_search_out);
+    const bool vec_t = (Tn & 3) == 0 && !misaligned(D.template_points) && !misaligned(D.idx_template_out);
+    for (int t = threadIdx.x; 4 * t < S; t += T)
+        resample_rows(vec_s, t, S, ns, ns, ps, ps, pl, index, 0u, epoch, D.seed_lo, D.seed_hi, D.search_points + (size_t)b * S * 3,
+                      D.cls_label + (size_t)b * S, D.idx_search_out ? D.idx_search_out + (size_t)b * S : nullptr);
+    for (int t = threadIdx.x; 4 * t < Tn; t += T)
+        resample_rows(vec_t, t, Tn, n1 + n2, n1, p1, p2, nullptr, index, 1u, epoch, D.seed_lo, D.seed_hi, D.template_points + (size_t)b * Tn * 3,
+                      nullptr, D.idx_template_out ? D.idx_template_out + (size_t)b * Tn : nullptr);
+}
+
 }  // namespace ptt
 
 using namespace ptt;
@@ -618,3 +752,24 @@ extern "C" int ptt_track_select_update(const float* proposals, int P, const int3
     return ptt_track_box_by_offset(boxes, n, est_out, 5, use_z, active, rng_pos);
 }
 
+
+extern "C" int ptt_train_batch_f32(const ptt_train_cand* cands_device, const ptt_train_batch_desc* desc_host, ptt_stream_t stream) {
+    if (!cands_device || !desc_host) return fail(PTT_EINVAL, "ptt_train_batch_f32: null pointer");
+    const ptt_train_batch_desc D = *desc_host;
+    if (D.B < 1 || D.n_cand < D.B || D.n_cand > PTT_TRAIN_MAX_CANDS || D.search_size < 1 || D.template_size < 1 || D.min_points < 2)
+        return fail(PTT_EINVAL, "ptt_train_batch_f32: B=%d n_cand=%d (B..%d) search_size=%d template_size=%d min_points=%d (>= 2)", D.B, D.n_cand,
+                    PTT_TRAIN_MAX_CANDS, D.search_size, D.template_size, D.min_points);
+    if (!D.search_points || !D.template_points || !D.cls_label || !D.reg_label || !D.src_out)
+        return fail(PTT_EINVAL, "ptt_train_batch_f32: null output");
+    hipLaunchKernelGGL((train_batch_kernel<256>), dim3(D.B), dim3(256), 0, as_stream(stream), cands_device, D);
+    return check_launch("train_batch_kernel");
+}
+
+extern "C" int ptt_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4) {
+    if (!counter4 || !key2 || !out4) return fail(PTT_EINVAL, "ptt_philox4x32_10: null pointer");
+    const uint32_t ctr[4] = {counter4[0], counter4[1], counter4[2], counter4[3]};
+    uint32_t out[4];
+    philox4x32_10(ctr, key2[0], key2[1], out);
+    for (int i = 0; i < 4; ++i) out4[i] = out[i];
+    return PTT_OK;
+}

@@ -797,6 +797,26 @@ def box_overlap(gt, pred, ref_coord, dims=3, out=None):
     return out[0], out[1]
 
 
+# --------------------------------------------------------------------------- N5: device-resident training batches
+TRAIN_CAND, TRAIN_BATCH_DESC = np.dtype(_lib.TrainCand), np.dtype(_lib.TrainBatchDesc)
+TRAIN_MAX_CANDS = _lib.PTT_TRAIN_MAX_CANDS
+
+
+def train_batch(cands_dev, desc, device):
+    """ptt_train_batch_f32: one training batch out of the crops of its candidates — `cands_dev` a device-resident table of
+    ptt_train_cand records (uint8 tensor, or a view into a larger table), `desc` a one-element TRAIN_BATCH_DESC array (host memory,
+    read before this returns). Enqueued on the current stream, behind the crop launch that fills the candidates' scratch."""
+    _launch("ptt_train_batch_f32", device, _ptr(cands_dev), ctypes.c_void_p(desc.ctypes.data), timed='ptt_train_batch_f32')
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on the host (ptt_philox4x32_10): four counter words, two key words -> four uint32 outputs."""
+    ctr, k, out = np.ascontiguousarray(counter, np.uint32), np.ascontiguousarray(key, np.uint32), np.empty(4, np.uint32)
+    assert ctr.shape == (4,) and k.shape == (2,)
+    _host_checked("ptt_philox4x32_10", ctr.ctypes.data, k.ctypes.data, out.ctypes.data)
+    return out
+
+
 # --------------------------------------------------------------------------- N3: training-step kernels (rows x channels)
 WGRAD2 = os.environ.get("PTT_WGRAD2", "1") != "0"        # dev A/B: the round-2 128 x 128-block weight-gradient kernel
 
