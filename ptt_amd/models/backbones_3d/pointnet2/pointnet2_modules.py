@@ -21,6 +21,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import ops, train_ops
+from ....param_cache import (DropsCachesOnModeChange, FoldedLayer, ParamCache, conv_bn_tensors, fold_conv_bn,
+                             index_table)
 from . import pointnet2_utils
 from . import pytorch_utils as pt_utils
 
@@ -43,7 +45,7 @@ STREAM_COMPACT_MIN_BALLS = 2048
 STREAM_COMPACT_MAX_POINTS = 1024
 
 
-class PointnetSAModuleVotes(nn.Module):
+class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
     def __init__(self, *, mlp: List[int], radius: float = None, nsample: int = None, bn: bool = True,
                  use_xyz: bool = True, normalize_xyz: bool = False, sample_uniformly: bool = False,
                  sample_method='fps'):
@@ -62,8 +64,7 @@ class PointnetSAModuleVotes(nn.Module):
             mlp_spec[0] += 3        # in place on the caller's list, exactly as the reference does (:51-53)
         self.mlp_module = pt_utils.SharedMLP(mlp_spec, bn=bn)
         self.sample_method = sample_method
-        self._fused_cache = None    # (key, [(wpacked, scale, shift, cin, cout, relu), ...])
-        self._arange_cache = None
+        self._fused_cache = ParamCache()
         self.centres_knn_k = 0      # > 0: a caller that runs a TransformerBlock on this level's centres (the box head) wants their
         self.centres_knn = None     #      kNN; at one frame it is formed in the sampling launch and left here (knn_idx, rel)
 
@@ -72,12 +73,7 @@ class PointnetSAModuleVotes(nn.Module):
         if self.sample_method == 'fps':
             return pointnet2_utils.furthest_point_sample(xyz, npoint)
         if self.sample_method in ('rs', 'sequence'):
-            # the same (B, npoint) index table every call: built once per shape (callers only read it)
-            cache = self.__dict__.setdefault('_sequence_cache', {})
-            key = (xyz.size(0), int(npoint), xyz.device)
-            if key not in cache:
-                cache[key] = torch.arange(npoint, dtype=torch.int32, device=xyz.device).repeat(xyz.size(0), 1)
-            return cache[key]
+            return index_table(xyz.size(0), npoint, xyz.device, torch.int32)
         if self.sample_method == 'ffps':
             raise NotImplementedError("sample_method 'ffps' needs furthest_point_sampling_with_dist, which the "
                                       "reference's extension never provided (tools/cfgs/kitti_models/ptt.yaml:42)")
@@ -109,62 +105,35 @@ class PointnetSAModuleVotes(nn.Module):
                 return ops.note_unfused(name, 'pre-activation units')
         return True
 
-    def train(self, mode=True):
-        # a train-mode forward updates the BatchNorm running statistics through raw pointers on some torch builds
-        # (no _version bump): drop the folded / packed parameters whenever the mode changes
-        if getattr(self, '_fused_cache', None) is not None:
-            ops.drop_params()
-        self._fused_cache = None
-        return super().train(mode)
-
     def _fused_params(self, device):
-        tensors = []
-        for unit in self.mlp_module:
-            tensors.append(unit.conv.weight)
-            if unit.conv.bias is not None:
-                tensors.append(unit.conv.bias)
-            if hasattr(unit, 'normlayer'):
-                bn = unit.normlayer.bn
-                tensors += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-                if bn.num_batches_tracked is not None:
-                    tensors.append(bn.num_batches_tracked)     # bumped by every train-mode forward
-        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
-        if self._fused_cache is not None and self._fused_cache[0] == key:
-            return self._fused_cache[1]
-        layers = []
-        with torch.no_grad():
-            for li, unit in enumerate(self.mlp_module):
-                w = unit.conv.weight
-                cout, cin = w.shape[0], w.shape[1]
-                rot = 3 if (li == 0 and self.use_xyz and cin > 3) else 0     # kernel row layout is [features | xyz]
-                scale = shift = None
-                if hasattr(unit, 'normlayer'):
-                    bn = unit.normlayer.bn
-                    scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).float().contiguous()
-                    shift = (bn.bias - bn.running_mean * scale).float().contiguous()
-                    if unit.conv.bias is not None:
-                        shift = (shift + unit.conv.bias * scale).contiguous()
-                elif unit.conv.bias is not None:
-                    shift = unit.conv.bias.detach().float().contiguous()
-                # the BatchNorm scale is folded into the packed weights: the kernels then start their accumulators at
-                # `shift` and the epilogue is a bare ReLU (every vector-ALU instruction outside the MFMA loop costs
-                # matrix time on gfx950). raw_scale stays available for the hoisted layer 0.
-                wq = w if scale is None else w * scale.view(-1, 1, 1, 1)
-                layers.append((ops.pack_weight(wq, rot), None, shift, cin, cout, hasattr(unit, 'activation'), scale))
-            # Layer 0 is linear in [rel ; f_n]: its feature half is evaluated once per POINT (N rows on the linear
-            # kernel) instead of once per (centre, neighbour) row; the kernel adds the 3 relative-coordinate terms.
-            hoist = None
-            w0 = self.mlp_module[0].conv.weight
-            if (self.use_xyz and len(layers) >= 2 and w0.shape[1] > 3 and layers[0][4] <= 256
-                    and os.environ.get('PTT_SA_HOIST', '1') != '0'):
-                w2 = w0.reshape(w0.shape[0], w0.shape[1]).float()
-                scale0 = layers[0][6]
-                wx = w2[:, 0:3] if scale0 is None else w2[:, 0:3] * scale0[:, None]
-                # the BatchNorm scale folded into both halves of layer 0 (no per-value scale in the linear launch's epilogue)
-                wf = w2[:, 3:] if scale0 is None else w2[:, 3:] * scale0[:, None]
-                hoist = (ops.pack_weight(wf.contiguous()), wx.t().contiguous(), layers[0][4], layers[0][5])
-        ops.publish_params(device)
-        self._fused_cache = (key, (layers, hoist))
+        """-> ([FoldedLayer, ...], hoist): the SharedMLP folded for ops.sa_fused_forward, and layer 0 split for the hoisted form
+        (wf_packed, wx, c0, relu0) or None."""
+        return self._fused_cache.get(conv_bn_tensors(self.mlp_module), device, self._fold)
+
+    def _fold(self):
+        layers, scale0 = [], None
+        for li, unit in enumerate(self.mlp_module):
+            w = unit.conv.weight
+            cout, cin = w.shape[0], w.shape[1]
+            rot = 3 if (li == 0 and self.use_xyz and cin > 3) else 0     # kernel row layout is [features | xyz]
+            scale, shift = fold_conv_bn(unit)
+            scale0 = scale if li == 0 else scale0                        # the hoisted layer 0 folds it into its own two packs
+            # the BatchNorm scale is folded into the packed weights: the kernels then start their accumulators at
+            # `shift` and the epilogue is a bare ReLU (every vector-ALU instruction outside the MFMA loop costs
+            # matrix time on gfx950)
+            wq = w if scale is None else w * scale.view(-1, 1, 1, 1)
+            layers.append(FoldedLayer(ops.pack_weight(wq, rot), None, shift, cin, cout, hasattr(unit, 'activation')))
+        # Layer 0 is linear in [rel ; f_n]: its feature half is evaluated once per POINT (N rows on the linear
+        # kernel) instead of once per (centre, neighbour) row; the kernel adds the 3 relative-coordinate terms.
+        hoist = None
+        w0 = self.mlp_module[0].conv.weight
+        if (self.use_xyz and len(layers) >= 2 and w0.shape[1] > 3 and layers[0].cout <= 256
+                and os.environ.get('PTT_SA_HOIST', '1') != '0'):
+            w2 = w0.reshape(w0.shape[0], w0.shape[1]).float()
+            wx = w2[:, 0:3] if scale0 is None else w2[:, 0:3] * scale0[:, None]
+            # the BatchNorm scale folded into both halves of layer 0 (no per-value scale in the linear launch's epilogue)
+            wf = w2[:, 3:] if scale0 is None else w2[:, 3:] * scale0[:, None]
+            hoist = (ops.pack_weight(wf.contiguous()), wx.t().contiguous(), layers[0].cout, layers[0].relu)
         return layers, hoist
 
     # ------------------------------------------------------------------ forward (reference :57-90)
@@ -175,11 +144,15 @@ class PointnetSAModuleVotes(nn.Module):
         when it runs one tracklet frame (ops.sa_levels_point_jobs).
         `compact` (same conditions): a level WITH point features pools each ball's real hits only (the stream shape of
         ops.sa_fused_forward, bitwise the same output) when the launch has at least STREAM_COMPACT_MIN_BALLS balls."""
-        fused = self._fusable(xyz, features)
-        if pre is not None and not fused:
-            pre = None
         self.centres_knn = None
-        if (fused and pre is None and inds is None and self.sample_method == 'fps' and xyz.shape[1] <= 256 and npoint <= 128
+        if self._fusable(xyz, features):
+            return self._forward_fused(xyz, features, npoint, inds, pre, compact)
+        return self._forward_train(xyz, features, npoint, inds)
+
+    def _forward_fused(self, xyz, features, npoint, inds, pre, compact):
+        """Eval mode on a HIP device: sampling and ball query (unless `pre` brings them), then the SharedMLP and the max over
+        the neighbours in ops.sa_fused_forward — or, for a handful of frames with a hoisted layer 0, in two row-job launches."""
+        if (pre is None and inds is None and self.sample_method == 'fps' and xyz.shape[1] <= 256 and npoint <= 128
                 and xyz.shape[0] * npoint * self.nsample <= ops.ONE_FRAME_MAX_SA_ROWS and self.centres_knn_k <= npoint):
             # a handful of frames (vote_aggregation at one tracklet frame): sampling, centre selection, ball query and the
             # centres' kNN in ONE launch (ptt_fps_ball_knn_f32) instead of three
@@ -189,64 +162,63 @@ class PointnetSAModuleVotes(nn.Module):
         prefix = inds is None and self.sample_method in ('rs', 'sequence')   # centres = the first npoint points
         if pre is not None:
             pass
-        elif fused and prefix:
+        elif prefix:
             # 'sequence' indices are constants of (B, npoint): build them once, not four tiny kernels per call
-            key = (xyz.size(0), npoint, str(xyz.device))
-            if self._arange_cache is None:
-                self._arange_cache = {}
-            if key not in self._arange_cache:          # search and template branches alternate (B, npoint)
-                self._arange_cache[key] = torch.arange(npoint, dtype=torch.int64, device=xyz.device).repeat(
-                    xyz.size(0), 1)
-                ops.publish_params(xyz.device, replaced=False)
-            inds64 = self._arange_cache[key]
+            inds64 = index_table(xyz.size(0), npoint, xyz.device, torch.int64)
         elif inds is None:
             inds = self._sample(xyz, features, npoint)
         else:
             assert inds.shape[1] == npoint
             inds = inds.to(torch.int32)
 
-        if fused:
-            xyz = xyz.contiguous()
-            if pre is not None:
-                new_xyz, idx, inds64 = pre
-            elif prefix:                                 # centres + ball query in one launch
-                new_xyz, _, idx = ops.centres_ball_query(xyz, None, npoint, self.radius, self.nsample)
-            else:
-                new_xyz, inds64, idx = ops.centres_ball_query(xyz, inds.contiguous(), npoint, self.radius, self.nsample)
-            layers, hoist = self._fused_params(xyz.device)
-            if hoist is not None and features is not None:
-                wf_packed, wx, c0, relu0 = hoist
-                rows = features.transpose(1, 2)                       # (B,N,C): contiguous when point-major
-                # rows with a padded stride (the one-frame head hands over 260-float rows) are read in place
-                uniform = rows.stride(2) == 1 and rows.stride(0) == rows.shape[1] * rows.stride(1)
-                term = ops.linear(rows if uniform else rows.contiguous(), wf_packed, c0, None, layers[0][2], relu=False)
-                B, M, ns = xyz.shape[0], npoint, self.nsample
-                if (B * M * ns <= ops.ONE_FRAME_MAX_SA_ROWS and ns in (16, 32) and len(layers) == 3 and c0 % 4 == 0 and c0 >= 192):
-                    # a handful of frames (vote_aggregation at one tracklet frame: 64 centres x 16 neighbours): the fused SA
-                    # kernel would be 16 workgroups with two chained 256 x 256 layers each (41 us); as two row-job launches
-                    # the 1024 grouped rows spread over the chip: layer 1 on rows built while its A tile is staged (term[idx]
-                    # + Wx . rel, ReLU), then layer 2 with the max over the neighbours as its epilogue
-                    L1, L2 = layers[1], layers[2]
-                    h = torch.empty((B * M * ns, L1[4]), dtype=torch.float32, device=xyz.device)
-                    ops.row_jobs([ops.row_job(L1[0], L1[4], prologue=3, x=term, idx=idx, xyz=xyz, centres=new_xyz, wx=wx,
-                                              radius=self.radius, ns=ns, M=M, N=xyz.shape[1], normalize_xyz=self.normalize_xyz,
-                                              pro_relu=relu0, scale=L1[1], shift=L1[2], act=1 if L1[5] else 0, out=h)])
-                    pooled = torch.empty((B, M, L2[4]), dtype=torch.float32, device=xyz.device)
-                    ops.row_jobs([ops.row_job(L2[0], L2[4], x=h, epilogue=2, ns=ns, M=M, scale=L2[1], shift=L2[2],
-                                              act=1 if L2[5] else 0, out=pooled)])
-                    return new_xyz, pooled.transpose(1, 2), inds64
-                new_features = ops.sa_fused_forward(xyz, new_xyz, idx, None, [L[:6] for L in layers[1:]], self.radius, True,
-                                                    self.normalize_xyz, point_major_out=True, l0=(term, wx, relu0),
-                                                    compact=(bool(compact) and B * M >= STREAM_COMPACT_MIN_BALLS
-                                                             and xyz.shape[1] <= STREAM_COMPACT_MAX_POINTS))
-            else:
-                # the level without point features (SA0) pools each ball's distinct rows only: same bits, a fraction of
-                # the rows (ball-query padding and the resampled clouds' repeated points)
-                new_features = ops.sa_fused_forward(xyz, new_xyz, idx, features, [L[:6] for L in layers], self.radius,
-                                                    self.use_xyz, self.normalize_xyz, point_major_out=True,
-                                                    compact=features is None)
-            return new_xyz, new_features, inds64
+        xyz = xyz.contiguous()
+        if pre is not None:
+            new_xyz, idx, inds64 = pre
+        elif prefix:                                 # centres + ball query in one launch
+            new_xyz, _, idx = ops.centres_ball_query(xyz, None, npoint, self.radius, self.nsample)
+        else:
+            new_xyz, inds64, idx = ops.centres_ball_query(xyz, inds.contiguous(), npoint, self.radius, self.nsample)
+        layers, hoist = self._fused_params(xyz.device)
+        if hoist is not None and features is not None:
+            wf_packed, wx, c0, relu0 = hoist
+            rows = features.transpose(1, 2)                       # (B,N,C): contiguous when point-major
+            # rows with a padded stride (the one-frame head hands over 260-float rows) are read in place
+            uniform = rows.stride(2) == 1 and rows.stride(0) == rows.shape[1] * rows.stride(1)
+            term = ops.linear(rows if uniform else rows.contiguous(), wf_packed, c0, None, layers[0].shift, relu=False)
+            B, M, ns = xyz.shape[0], npoint, self.nsample
+            if (B * M * ns <= ops.ONE_FRAME_MAX_SA_ROWS and ns in (16, 32) and len(layers) == 3 and c0 % 4 == 0 and c0 >= 192):
+                # a handful of frames (vote_aggregation at one tracklet frame: 64 centres x 16 neighbours): the fused SA
+                # kernel would be 16 workgroups with two chained 256 x 256 layers each (41 us); as two row-job launches
+                # the 1024 grouped rows spread over the chip: layer 1 on rows built while its A tile is staged (term[idx]
+                # + Wx . rel, ReLU), then layer 2 with the max over the neighbours as its epilogue
+                L1, L2 = layers[1], layers[2]
+                h = torch.empty((B * M * ns, L1.cout), dtype=torch.float32, device=xyz.device)
+                ops.row_jobs([pt_utils.layer_job(L1, prologue=3, x=term, idx=idx, xyz=xyz, centres=new_xyz, wx=wx,
+                                                 radius=self.radius, ns=ns, M=M, N=xyz.shape[1], normalize_xyz=self.normalize_xyz,
+                                                 pro_relu=relu0, out=h)])
+                pooled = torch.empty((B, M, L2.cout), dtype=torch.float32, device=xyz.device)
+                ops.row_jobs([pt_utils.layer_job(L2, x=h, epilogue=2, ns=ns, M=M, out=pooled)])
+                return new_xyz, pooled.transpose(1, 2), inds64
+            new_features = ops.sa_fused_forward(xyz, new_xyz, idx, None, layers[1:], self.radius, True,
+                                                self.normalize_xyz, point_major_out=True, l0=(term, wx, relu0),
+                                                compact=(bool(compact) and B * M >= STREAM_COMPACT_MIN_BALLS
+                                                         and xyz.shape[1] <= STREAM_COMPACT_MAX_POINTS))
+        else:
+            # the level without point features (SA0) pools each ball's distinct rows only: same bits, a fraction of
+            # the rows (ball-query padding and the resampled clouds' repeated points)
+            new_features = ops.sa_fused_forward(xyz, new_xyz, idx, features, layers, self.radius,
+                                                self.use_xyz, self.normalize_xyz, point_major_out=True,
+                                                compact=features is None)
+        return new_xyz, new_features, inds64
 
+    def _forward_train(self, xyz, features, npoint, inds):
+        """Training mode, the CPU, and the eval-mode calls _fusable turned away: the hoisted training forms of
+        train_ops where they apply, else the reference's op sequence."""
+        if inds is None:
+            inds = self._sample(xyz, features, npoint)
+        else:
+            assert inds.shape[1] == npoint
+            inds = inds.to(torch.int32)
         hoist = (self.use_xyz and not self.sample_uniformly and self.nsample * npoint <= 16384
                  and train_ops.usable(self.mlp_module, xyz if features is None else features)
                  and self.mlp_module[0].conv.weight.shape[0] % 4 == 0)

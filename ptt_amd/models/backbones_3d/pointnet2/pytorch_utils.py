@@ -8,8 +8,13 @@ state_dict entries by key and shape): a unit is an nn.Sequential with children `
 `layer0`, `layer1`, ... Parameters are initialised as the reference does (kaiming-normal conv
 weights, BN weight 1 / bias 0, no conv bias when BN follows).
 """
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
+
+from .... import ops
+from ....param_cache import DropsCachesOnModeChange, FoldedLayer, ParamCache, conv_bn_tensors, fold_conv_bn
 
 
 class _Norm(nn.Sequential):
@@ -120,7 +125,7 @@ class SharedMLP(nn.Sequential):
                        preact=preact))
 
 
-class Seq(nn.Sequential):
+class Seq(DropsCachesOnModeChange, nn.Sequential):
     """Fluent builder the heads use: Seq(c).conv1d(c1, bn=True).conv1d(c2, activation=None) (reference :263-427).
     Children are named by their position, which is what the reference's checkpoints contain."""
 
@@ -128,6 +133,8 @@ class Seq(nn.Sequential):
         super().__init__()
         self.count = 0
         self.current_channels = input_channels
+        self._rows_cache = ParamCache()     # the eval-mode folded layers (_rows_params); dropped by train() / eval()
+        self._rows_rot_caches = {}          # rot0 -> ParamCache of layer 0's weight packed rotated (rows_layers): no BatchNorm in it, train() leaves it
 
     def _push(self, module, out_size):
         self.add_module(str(self.count), module)
@@ -162,7 +169,6 @@ class Seq(nn.Sequential):
 # BatchNorm folded from its running statistics, instead of conv + batch_norm + relu (+ layout copies) per layer.
 # ---------------------------------------------------------------------------------------------------------------
 def rows_fusable(seq, rows):
-    from .... import ops
     if seq.training or not rows.is_cuda:
         return False
     name = 'Conv1d stack %s' % [u.conv.weight.shape[0] for u in seq if hasattr(u, 'conv')]
@@ -183,60 +189,43 @@ def rows_fusable(seq, rows):
     return len(seq) > 0
 
 
+# A Conv1d stack's layer folded both ways: `linear` for the per-layer launches (ptt_linear_f32 / ptt_row_jobs_f32: BatchNorm
+# scale and shift in the epilogue), `fused` for the one-launch form (ptt_rows_mlp_f32: the scale folded into the packed weights)
+RowsLayer = namedtuple('RowsLayer', 'linear fused')
+
+
 def _rows_params(seq):
-    from .... import ops
-    tensors = []
-    for unit in seq:
-        tensors.append(unit.conv.weight)
-        if unit.conv.bias is not None:
-            tensors.append(unit.conv.bias)
-        if hasattr(unit, 'normlayer'):
-            bn = unit.normlayer.bn
-            tensors += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-            if bn.num_batches_tracked is not None:
-                tensors.append(bn.num_batches_tracked)         # bumped by every train-mode forward
-    key = tuple((t.data_ptr(), t._version) for t in tensors)
-    cache = getattr(seq, '_rows_cache', None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    layers = []
-    with torch.no_grad():
+    def build():
+        layers = []
         for unit in seq:
             w = unit.conv.weight
-            scale = shift = None
-            if hasattr(unit, 'normlayer'):
-                bn = unit.normlayer.bn
-                scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).float().contiguous()
-                shift = (bn.bias - bn.running_mean * scale).float().contiguous()
-                if unit.conv.bias is not None:
-                    shift = (shift + unit.conv.bias * scale).contiguous()
-            elif unit.conv.bias is not None:
-                shift = unit.conv.bias.detach().float().contiguous()
+            scale, shift = fold_conv_bn(unit)
             w2 = w.reshape(w.shape[0], w.shape[1])
-            layers.append((ops.pack_weight(w2), w.shape[0], scale, shift, hasattr(unit, 'activation'),
-                           # the one-launch form (ptt_rows_mlp_f32): BatchNorm scale folded into the packed weights
-                           ops.pack_weight(w2 if scale is None else w2 * scale[:, None]), w.shape[1]))
-    ops.publish_params(layers[0][0].device)
-    object.__setattr__(seq, '_rows_cache', (key, layers))
-    return layers
+            linear = FoldedLayer(ops.pack_weight(w2), scale, shift, w.shape[1], w.shape[0], hasattr(unit, 'activation'))
+            layers.append(RowsLayer(linear, linear._replace(
+                wpacked=ops.pack_weight(w2 if scale is None else w2 * scale[:, None]), scale=None)))
+        return layers
+    tensors = conv_bn_tensors(seq)
+    return seq._rows_cache.get(tensors, tensors[0].device, build)
 
 
 def rows_layers(seq, rot0=0):
-    """The folded layers of an eval-mode Conv1d stack for ptt_row_jobs_f32: [(wpacked, cout, scale, shift, relu), ...].
+    """The folded layers of an eval-mode Conv1d stack for ptt_row_jobs_f32: [FoldedLayer, ...] (BatchNorm in scale / shift).
     rot0: the first layer's input channels rotated left by rot0 before packing — a stack whose reference input is
     cat((xyz, feats)) (centroids_voting_head.py:86-90) then reads [feats | xyz], two tensors, no concatenation."""
-    from .... import ops
-    layers = [L[:5] for L in _rows_params(seq)]
+    layers = [L.linear for L in _rows_params(seq)]
     if rot0:
-        cache = getattr(seq, '_rows_rot_cache', None)
-        key = (id(layers[0][0]), rot0)
-        if cache is None or cache[0] != key:
-            w = seq[0].conv.weight
-            cache = (key, ops.pack_weight(w.reshape(w.shape[0], w.shape[1]), rot0))
-            ops.publish_params(w.device)
-            object.__setattr__(seq, '_rows_rot_cache', cache)
-        layers[0] = (cache[1],) + tuple(layers[0][1:])
+        w = seq[0].conv.weight
+        cache = seq._rows_rot_caches.setdefault(rot0, ParamCache())
+        layers[0] = layers[0]._replace(wpacked=cache.get(
+            [w], w.device, lambda: ops.pack_weight(w.reshape(w.shape[0], w.shape[1]), rot0)))
     return layers
+
+
+def layer_job(L, **kw):
+    """ops.row_job for one FoldedLayer: its packed weights, width, scale / shift and ReLU, plus the job's own arguments."""
+    kw.setdefault('act', 1 if L.relu else 0)
+    return ops.row_job(L.wpacked, L.cout, scale=L.scale, shift=L.shift, **kw)
 
 
 def _one_launch(layers, rows):
@@ -245,20 +234,19 @@ def _one_launch(layers, rows):
     per-layer launches spread each layer's column tiles over idle CUs. At one tracklet frame (128 rows) the per-layer form
     is faster (1.12 vs 1.14 ms per frame); at 48 frames the one-launch form (4.19 vs 4.21 ms per step)."""
     n_rows = rows.numel() // rows.shape[-1]
-    return (n_rows >= 1024 and len(layers) <= 4 and rows.shape[-1] <= 264 and all(L[1] <= 256 for L in layers[:-1])
-            and layers[-1][1] <= 384)
+    return (n_rows >= 1024 and len(layers) <= 4 and rows.shape[-1] <= 264 and all(L.fused.cout <= 256 for L in layers[:-1])
+            and layers[-1].fused.cout <= 384)
 
 
 def rows_forward(seq, rows, residual=None):
     """seq(rows^T)^T for an eval-mode Conv1d(k=1) stack: rows (..., Cin) -> (..., Cout); `residual` (..., Cout) is
     added to the last layer's output. Call only when rows_fusable(seq, rows). The whole stack is one launch when it fits
     ptt_rows_mlp_f32, else one ptt_linear_f32 launch per layer."""
-    from .... import ops
     layers = _rows_params(seq)
     if _one_launch(layers, rows) and rows.stride(-1) == 1:
-        return ops.rows_mlp(rows, [(L[5], None, L[3], L[6], L[1], L[4]) for L in layers], residual)
+        return ops.rows_mlp(rows, [L.fused for L in layers], residual)
     x = rows
     for i, L in enumerate(layers):
-        wp, cout, scale, shift, relu = L[:5]
-        x = ops.linear(x, wp, cout, scale, shift, relu, residual if i == len(layers) - 1 else None)
+        L = L.linear
+        x = ops.linear(x, L.wpacked, L.cout, L.scale, L.shift, L.relu, residual if i == len(layers) - 1 else None)
     return x

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from ... import graph_policy, ops, train_ops
+from ...param_cache import ParamCache, index_table
 from .pointnet2 import pointnet2_modules
 
 
@@ -34,7 +35,7 @@ class PointNet2BackboneLight(nn.Module):
                 sample_method=sa.SAMPLE_METHOD[k]))
         self.cov_final = nn.Conv1d(256, 256, kernel_size=1)
         self.num_point_features = sa.MLPS[-1][-1]
-        self._cov_cache = None
+        self._cov_cache = ParamCache()
         self.seed_knn = 16          # neighbours of the seeds' kNN formed beside the ball queries at one frame (0: not formed);
         #                             the tracker sets it to its centroid head's transformer's k
         self.overlap_branches = True
@@ -60,21 +61,10 @@ class PointNet2BackboneLight(nn.Module):
             ops.note_unfused('PointNet2BackboneLight.cov_final', 'autograd is recording or input is not float32')
             return self.cov_final(features)
         w, b = self.cov_final.weight, self.cov_final.bias
-        key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
-        if self._cov_cache is None or self._cov_cache[0] != key:
-            self._cov_cache = (key, ops.pack_weight(w), b.detach().float().contiguous())
-            ops.publish_params(w.device)
+        wpacked, bias = self._cov_cache.get([w, b], w.device, lambda: (ops.pack_weight(w), b.detach().float().contiguous()))
         rows = features.transpose(1, 2)                        # (B,M,C); contiguous when point-major
-        out = ops.linear(rows, self._cov_cache[1], w.shape[0], None, self._cov_cache[2])
+        out = ops.linear(rows, wpacked, w.shape[0], None, bias)
         return out.transpose(1, 2)                              # (B,C,M) view
-
-    def _arange64(self, xyz, n):
-        key = (xyz.size(0), n, str(xyz.device))
-        cache = self.__dict__.setdefault('_arange_cache', {})
-        if key not in cache:
-            cache[key] = torch.arange(n, dtype=torch.int64, device=xyz.device).repeat(xyz.size(0), 1)
-            ops.publish_params(xyz.device, replaced=False)
-        return cache[key]
 
     def branch_forward(self, pts, npoints: List, inds0=None, want_knn=0, compact_levels=()):
         """`inds0`: optional precomputed level-0 sample indices (B, npoints[0]) — the SA module accepts
@@ -102,7 +92,7 @@ class PointNet2BackboneLight(nn.Module):
             inds0 = inds0.to(torch.int32).contiguous()
             levels, inds64, knn = ops.sa_levels_point_jobs(xyz, inds0, list(npoints), list(sa.RADIUS), list(sa.NSAMPLE),
                                                            knn_k=want_knn)
-            seq = [None, self._arange64(xyz, npoints[1]), self._arange64(xyz, npoints[2])]
+            seq = [None] + [index_table(xyz.size(0), n, xyz.device, torch.int64) for n in npoints[1:3]]
             xyz, features, inds0 = self.SA_modules[0](xyz=xyz, features=features, npoint=npoints[0], inds=inds0,
                                                       pre=(levels[0][0], levels[0][1], inds64))
             xyz, features, inds1 = self.SA_modules[1](xyz=xyz, features=features, npoint=npoints[1],

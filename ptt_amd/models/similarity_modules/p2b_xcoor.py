@@ -14,10 +14,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops, train_ops
+from ...param_cache import DropsCachesOnModeChange, FoldedLayer, ParamCache, fold_conv_bn
 from ..backbones_3d.pointnet2 import pytorch_utils as layer_utils
 
 
-class CosineSimAug(nn.Module):
+class CosineSimAug(DropsCachesOnModeChange, nn.Module):
     def __init__(self, model_cfg):
         super().__init__()
         self.model_cfg = model_cfg
@@ -28,7 +29,7 @@ class CosineSimAug(nn.Module):
             .conv1d(self.model_cfg.CONV.CHANNELS[1], bn=self.model_cfg.CONV.BN)
             .conv1d(self.model_cfg.CONV.CHANNELS[2], activation=None)
         )
-        self._cache = None
+        self._cache = ParamCache()
 
     # ------------------------------------------------------------------ fused-path parameters
     def _fusable(self, search_feats, template_feats):
@@ -57,42 +58,25 @@ class CosineSimAug(nn.Module):
             return ops.note_unfused(name, 'first SharedMLP layer does not take 1 + 3 + C channels')
         return True
 
-    def train(self, mode=True):
-        if getattr(self, '_cache', None) is not None:
-            ops.drop_params()
-        self._cache = None          # BatchNorm running statistics may change without a _version bump in train mode
-        return super().train(mode)
-
-    @staticmethod
-    def _fold(unit):
-        bn = unit.normlayer.bn
-        scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).float().contiguous()
-        shift = (bn.bias - bn.running_mean * scale).float().contiguous()
-        return scale, shift
-
     def _params(self):
         ts = list(self.state_dict().values())         # incl. num_batches_tracked: bumped by every train-mode forward
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._cache is not None and self._cache[0] == key:
-            return self._cache[1]
-        with torch.no_grad():
-            units = list(self.mlp)
-            w0 = units[0].conv.weight.reshape(units[0].conv.weight.shape[0], -1)       # (C0, 1 + 3 + C)
-            s0, t0 = self._fold(units[0])
-            layers = []
-            for u in units[1:]:
-                sc, sh = self._fold(u)
-                w = u.conv.weight
-                # BatchNorm scale folded into the packed weights: the kernel starts its accumulators at the shift
-                layers.append((ops.pack_weight(w * sc.view(-1, 1, 1, 1)), None, sh, w.shape[1], w.shape[0], True))
-            # layer 0's BatchNorm is folded into its two halves: the per-template-point term comes out of the linear
-            # kernel as s0 * (W0[:,1:] . [xyz;feat]) + t0, the similarity column as s0 * w_sim
-            P = dict(w_sim=(w0[:, 0].float() * s0).contiguous(), w_rest=ops.pack_weight(w0[:, 1:]), c0=w0.shape[0],
-                     w_rest_fx=ops.pack_weight(w0[:, 1:], 3),      # the same weights for rows laid out [feats | xyz]
-                     scale0=s0, shift0=t0, layers=layers)
-        ops.publish_params(self.conv[0].conv.weight.device)
-        self._cache = (key, P)
-        return P
+        return self._cache.get(ts, ts[0].device, self._fold)
+
+    def _fold(self):
+        units = list(self.mlp)
+        w0 = units[0].conv.weight.reshape(units[0].conv.weight.shape[0], -1)       # (C0, 1 + 3 + C)
+        s0, t0 = fold_conv_bn(units[0])
+        layers = []
+        for u in units[1:]:
+            sc, sh = fold_conv_bn(u)
+            w = u.conv.weight
+            # BatchNorm scale folded into the packed weights: the kernel starts its accumulators at the shift
+            layers.append(FoldedLayer(ops.pack_weight(w * sc.view(-1, 1, 1, 1)), None, sh, w.shape[1], w.shape[0], True))
+        # layer 0's BatchNorm is folded into its two halves: the per-template-point term comes out of the linear
+        # kernel as s0 * (W0[:,1:] . [xyz;feat]) + t0, the similarity column as s0 * w_sim
+        return dict(w_sim=(w0[:, 0].float() * s0).contiguous(), w_rest=ops.pack_weight(w0[:, 1:]), c0=w0.shape[0],
+                    w_rest_fx=ops.pack_weight(w0[:, 1:], 3),      # the same weights for rows laid out [feats | xyz]
+                    scale0=s0, shift0=t0, layers=layers)
 
     def forward(self, batch_dict):
         search_feats = batch_dict['search_feats']            # (B,f,n2)
@@ -126,10 +110,9 @@ class CosineSimAug(nn.Module):
                 L = layer_utils.rows_layers(self.conv)
                 h0, h1 = fused[0].transpose(1, 2), fused[1].transpose(1, 2)                  # (B,n2,C) contiguous rows
                 x = None
-                for li, (wp, cout, scale, shift, relu) in enumerate(L):
-                    y = torch.empty((b, n2, cout), dtype=torch.float32, device=h0.device)
-                    ops.row_jobs([ops.row_job(wp, cout, x=h0 if li == 0 else x, xmax=h1 if li == 0 else None, scale=scale, shift=shift,
-                                              act=1 if relu else 0, out=y)])
+                for li, layer in enumerate(L):
+                    y = torch.empty((b, n2, layer.cout), dtype=torch.float32, device=h0.device)
+                    ops.row_jobs([layer_utils.layer_job(layer, x=h0 if li == 0 else x, xmax=h1 if li == 0 else None, out=y)])
                     x = y
             else:
                 y = layer_utils.rows_forward(self.conv, fused.transpose(1, 2))               # both convolutions, one launch

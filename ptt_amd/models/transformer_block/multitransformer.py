@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops, train_ops
+from ...param_cache import ParamCache
 from ..model_utils import get_clones, index_points, square_distance
 from .variants import PER_LAYER_MAX_POINTS, SPATIAL_ORDER_MIN_POINTS, _rows2d
 
@@ -51,7 +52,7 @@ class MulHeadTransformerLayer(nn.Module):
         self.d_model = d_model
         self.d_points = d_points
         self.head_dim = head_dim
-        self._cache = None
+        self._cache = ParamCache()
 
     # ---------------------------------------------------------------- fused-path parameters
     def _params(self):
@@ -59,33 +60,29 @@ class MulHeadTransformerLayer(nn.Module):
               self.w_vs.weight, self.fc_delta[0].weight, self.fc_delta[0].bias, self.fc_delta[2].weight,
               self.fc_delta[2].bias, self.fc_gamma[0].weight, self.fc_gamma[0].bias, self.fc_gamma[2].weight,
               self.fc_gamma[2].bias, self.proj.weight, self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._cache is not None and self._cache[0] == key:
-            return self._cache[1]
-        with torch.no_grad():
-            f = lambda t: t.detach().float().contiguous()
-            H = self.heads
-            # fc1 folded into the q|k|v projection, as TransformerBlock._params does (product in f64)
-            wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
-            # the one-frame chain runs fc_gamma on the row-job kernel as its block-diagonal D x D expansion (diagonal blocks =
-            # the shared hd x hd weight); the pair kernel reads the hd x hd weights themselves
-            blockdiag = lambda wt: torch.block_diag(*([f(wt)] * H)).contiguous()
-            P = dict(
-                qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
-                qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
-                wd1=ops.pack_delta0(self.fc_delta[0].weight, self.fc_delta[0].bias),
-                wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
-                wg1=ops.pack_weight(self.fc_gamma[0].weight), wg2=ops.pack_weight(self.fc_gamma[2].weight),
-                bg1=f(self.fc_gamma[0].bias).repeat(H).contiguous(), bg2=f(self.fc_gamma[2].bias).repeat(H).contiguous(),
-                wg1_bd=ops.pack_weight(blockdiag(self.fc_gamma[0].weight)),
-                wg2_bd=ops.pack_weight(blockdiag(self.fc_gamma[2].weight)),
-                w1b=torch.cat((f(self.fc_delta[0].weight), f(self.fc_delta[0].bias)[:, None]), 1).contiguous(),
-                proj=ops.pack_weight(self.proj.weight),
-                fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias),
-                n1w=f(self.norm1.weight), n1b=f(self.norm1.bias), n2w=f(self.norm2.weight), n2b=f(self.norm2.bias))
-        ops.publish_params(self.fc1.weight.device)
-        self._cache = (key, P)
-        return P
+        return self._cache.get(ts, ts[0].device, self._pack)
+
+    def _pack(self):
+        f = lambda t: t.detach().float().contiguous()
+        H = self.heads
+        # fc1 folded into the q|k|v projection, as TransformerBlock._params does (product in f64)
+        wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
+        # the one-frame chain runs fc_gamma on the row-job kernel as its block-diagonal D x D expansion (diagonal blocks =
+        # the shared hd x hd weight); the pair kernel reads the hd x hd weights themselves
+        blockdiag = lambda wt: torch.block_diag(*([f(wt)] * H)).contiguous()
+        return dict(
+            qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
+            qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
+            wd1=ops.pack_delta0(self.fc_delta[0].weight, self.fc_delta[0].bias),
+            wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
+            wg1=ops.pack_weight(self.fc_gamma[0].weight), wg2=ops.pack_weight(self.fc_gamma[2].weight),
+            bg1=f(self.fc_gamma[0].bias).repeat(H).contiguous(), bg2=f(self.fc_gamma[2].bias).repeat(H).contiguous(),
+            wg1_bd=ops.pack_weight(blockdiag(self.fc_gamma[0].weight)),
+            wg2_bd=ops.pack_weight(blockdiag(self.fc_gamma[2].weight)),
+            w1b=torch.cat((f(self.fc_delta[0].weight), f(self.fc_delta[0].bias)[:, None]), 1).contiguous(),
+            proj=ops.pack_weight(self.proj.weight),
+            fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias),
+            n1w=f(self.norm1.weight), n1b=f(self.norm1.bias), n2w=f(self.norm2.weight), n2b=f(self.norm2.bias))
 
     def _fused(self, xyz, features, knn_idx, rel, want_attn, order):
         """One layer on the HIP kernels; the caller has checked MulTransformerBlock._fusable and formed the kNN."""

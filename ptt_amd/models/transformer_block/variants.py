@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops, train_ops
+from ...param_cache import ParamCache
 from ..model_utils import index_points, square_distance
 
 
@@ -54,7 +55,7 @@ class TransformerBlock(nn.Module):
         self.k = k
         self.d_model = d_model
         self.d_points = d_points
-        self._cache = None
+        self._cache = ParamCache()
 
     # ---------------------------------------------------------------- fused-path parameters
     def _fusable(self, xyz, features):
@@ -78,27 +79,23 @@ class TransformerBlock(nn.Module):
               self.w_vs.weight, self.fc_delta[0].weight, self.fc_delta[0].bias, self.fc_delta[2].weight,
               self.fc_delta[2].bias, self.fc_gamma[0].weight, self.fc_gamma[0].bias, self.fc_gamma[2].weight,
               self.fc_gamma[2].bias]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._cache is not None and self._cache[0] == key:
-            return self._cache[1]
-        with torch.no_grad():
-            f = lambda t: t.detach().float().contiguous()
-            # fc1 has no activation and only feeds w_qs / w_ks / w_vs (variants.py:155-156), so the two linear maps
-            # are one: [q|k|v] = (W_qkv W_1) f + W_qkv b_1 — 256 -> 1536 instead of 256 -> 512 -> 1536 (product in f64)
-            wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
-            P = dict(
-                qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
-                qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
-                wd1=ops.pack_delta0(self.fc_delta[0].weight, self.fc_delta[0].bias),
-                wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
-                wg1=ops.pack_weight(self.fc_gamma[0].weight), bg1=f(self.fc_gamma[0].bias),
-                wg2=ops.pack_weight(self.fc_gamma[2].weight), bg2=f(self.fc_gamma[2].bias),
-                fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias),
-                wd1_lin=ops.pack_weight(self.fc_delta[0].weight), bd1=f(self.fc_delta[0].bias),
-                w1b=torch.cat((f(self.fc_delta[0].weight), f(self.fc_delta[0].bias)[:, None]), 1).contiguous())
-        ops.publish_params(self.fc1.weight.device)
-        self._cache = (key, P)
-        return P
+        return self._cache.get(ts, ts[0].device, self._pack)
+
+    def _pack(self):
+        f = lambda t: t.detach().float().contiguous()
+        # fc1 has no activation and only feeds w_qs / w_ks / w_vs (variants.py:155-156), so the two linear maps
+        # are one: [q|k|v] = (W_qkv W_1) f + W_qkv b_1 — 256 -> 1536 instead of 256 -> 512 -> 1536 (product in f64)
+        wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
+        return dict(
+            qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
+            qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
+            wd1=ops.pack_delta0(self.fc_delta[0].weight, self.fc_delta[0].bias),
+            wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
+            wg1=ops.pack_weight(self.fc_gamma[0].weight), bg1=f(self.fc_gamma[0].bias),
+            wg2=ops.pack_weight(self.fc_gamma[2].weight), bg2=f(self.fc_gamma[2].bias),
+            fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias),
+            wd1_lin=ops.pack_weight(self.fc_delta[0].weight), bd1=f(self.fc_delta[0].bias),
+            w1b=torch.cat((f(self.fc_delta[0].weight), f(self.fc_delta[0].bias)[:, None]), 1).contiguous())
 
     # xyz: b x n x 3, features: b x n x f
     def forward(self, xyz, features, knn=None, want_attn=True):
@@ -227,7 +224,7 @@ class TransformerBlockSTD(nn.Module):
         self.k = k
         self.d_model = d_model
         self.d_points = d_points
-        self._cache = None
+        self._cache = ParamCache()
 
     def _fusable(self, xyz, features):
         if self.training or not xyz.is_cuda:
@@ -242,20 +239,16 @@ class TransformerBlockSTD(nn.Module):
     def _params(self):
         ts = [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.w_qs.weight, self.w_ks.weight,
               self.w_vs.weight, self.fc_delta[0].weight, self.fc_delta[0].bias, self.fc_delta[2].weight, self.fc_delta[2].bias]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._cache is not None and self._cache[0] == key:
-            return self._cache[1]
-        with torch.no_grad():
-            f = lambda t: t.detach().float().contiguous()
-            wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
-            P = dict(qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
-                     qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
-                     wd1=ops.pack_weight(self.fc_delta[0].weight), bd1=f(self.fc_delta[0].bias),
-                     wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
-                     fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias))
-        ops.publish_params(self.fc1.weight.device)
-        self._cache = (key, P)
-        return P
+        return self._cache.get(ts, ts[0].device, self._pack)
+
+    def _pack(self):
+        f = lambda t: t.detach().float().contiguous()
+        wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
+        return dict(qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
+                    qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
+                    wd1=ops.pack_weight(self.fc_delta[0].weight), bd1=f(self.fc_delta[0].bias),
+                    wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
+                    fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias))
 
     def forward(self, xyz, features, knn=None, want_attn=True):
         # `knn`: the callers hand every block the neighbour table formed beside their sampling; full attention has no use for it.

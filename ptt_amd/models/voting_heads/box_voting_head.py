@@ -101,18 +101,17 @@ class BoxVotingHead(VotingHeadTemplate):
                 L = layer_utils.rows_layers(self.refine_layer)
                 B, M, _ = rows.shape
                 x = rows.contiguous()
-                for wp, cout, scale, shift, relu in L[:-1]:
-                    h = torch.empty((B * M, cout), dtype=torch.float32, device=rows.device)
-                    ops.row_jobs([ops.row_job(wp, cout, x=x, scale=scale, shift=shift, act=1 if relu else 0, out=h)])
+                for layer in L[:-1]:
+                    h = torch.empty((B * M, layer.cout), dtype=torch.float32, device=rows.device)
+                    ops.row_jobs([layer_utils.layer_job(layer, x=x, out=h)])
                     x = h
-                wp, cout, scale, shift, relu = L[-1]
+                cout = L[-1].cout
                 # pred_box_out (set by a driver: ptt_amd.tracklet_runner): a preallocated (B,M,5) buffer to write the proposals
                 # into, so that its one read-back per frame needs no gathering copy
                 boxes = getattr(self, 'pred_box_out', None)
                 if boxes is None or tuple(boxes.shape) != (B, M, cout) or boxes.device != rows.device:
                     boxes = torch.empty((B, M, cout), dtype=torch.float32, device=rows.device)
-                ops.row_jobs([ops.row_job(wp, cout, x=x, scale=scale, shift=shift, act=1 if relu else 0, res2=centres.contiguous(),
-                                          res_split=3, out=boxes)])
+                ops.row_jobs([layer_utils.layer_job(L[-1], x=x, res2=centres.contiguous(), res_split=3, out=boxes)])
                 batch_dict['pred_box_center'] = centres
                 batch_dict['pred_box_data'] = boxes
                 return batch_dict

@@ -111,21 +111,16 @@ class CentroidVotingHead(VotingHeadTemplate):
         cla = layer_utils.rows_layers(self.cla_layer, 3 if cls_xyz else 0)
         vote = layer_utils.rows_layers(self.vote_layer, 3)
         new = lambda c: torch.empty((B * N, c), dtype=torch.float32, device=dev)
-        hc, hv = [new(cla[0][1]), new(cla[1][1])], [new(vote[0][1]), new(vote[1][1])]
+        hc, hv = [new(cla[0].cout), new(cla[1].cout)], [new(vote[0].cout), new(vote[1].cout)]
         ld = (1 + C + 3) // 4 * 4                                               # votes_feats rows padded to 16 bytes
         vfeats = torch.empty((B, N, ld), dtype=torch.float32, device=dev)
         votes = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
         cls_raw = torch.empty((B * N, 1), dtype=torch.float32, device=dev)
-
-        def job(L, x, out, x2=None, **kw):
-            wp, cout, scale, shift, relu = L
-            return ops.row_job(wp, cout, x=x, x2=x2, scale=scale, shift=shift, act=1 if relu else 0, out=out, **kw)
-
-        ops.row_jobs([job(cla[0], rows, hc[0], seeds if cls_xyz else None), job(vote[0], rows, hv[0], seeds)])
-        ops.row_jobs([job(cla[1], hc[0], hc[1]), job(vote[1], hv[0], hv[1])])
-        wp, cout, scale, shift, _ = cla[2]
-        ops.row_jobs([ops.row_job(wp, cout, x=hc[1], scale=scale, shift=shift, act=2, out=vfeats.view(B * N, ld)[:, 0:1], raw=cls_raw),
-                      job(vote[2], hv[1], vfeats.view(B * N, ld), res=rows, res2=seeds, res_split=3, out_col0=1, out2=votes,
+        job = layer_utils.layer_job
+        ops.row_jobs([job(cla[0], x=rows, out=hc[0], x2=seeds if cls_xyz else None), job(vote[0], x=rows, out=hv[0], x2=seeds)])
+        ops.row_jobs([job(cla[1], x=hc[0], out=hc[1]), job(vote[1], x=hv[0], out=hv[1])])
+        ops.row_jobs([job(cla[2], x=hc[1], act=2, out=vfeats.view(B * N, ld)[:, 0:1], raw=cls_raw),
+                      job(vote[2], x=hv[1], out=vfeats.view(B * N, ld), res=rows, res2=seeds, res_split=3, out_col0=1, out2=votes,
                           out_split=3)])
         batch_dict['pred_centroids_cls'] = cls_raw.view(B, N).squeeze(0)
         batch_dict['pred_centroids_votes'] = votes

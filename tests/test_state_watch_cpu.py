@@ -39,9 +39,25 @@ def test_state_watch_sees_cache_rebuilds_and_drops():
     assert w.changed()
     w.mark()
     sa = m.vote_aggregation
-    sa._fused_cache = ('key', 'layers')                         # as if an eval forward had built it
+    sa._fused_cache.get([], torch.device('cpu'), lambda: 'layers')      # as if an eval forward had built it
+    w.mark()
     m.train()                                                   # ... and train() frees it
-    assert w.changed() and sa._fused_cache is None
+    assert w.changed() and not sa._fused_cache.held()
+    w.mark()
+    m.eval()
+    assert not w.changed()
+
+
+def test_state_watch_sees_a_voting_heads_conv1d_stack_dropped():
+    from ptt_amd.config import StubDataset, ptt_model_cfg
+    from ptt_amd.models import build_network
+    m = build_network(ptt_model_cfg(), 1, StubDataset()).eval()
+    w = ops.StateWatch(m)
+    stack = m.centroid_voting_head.vote_layer
+    stack._rows_cache.get([], torch.device('cpu'), lambda: 'layers')    # as if an eval forward had folded its BatchNorm
+    w.mark()
+    m.train()
+    assert w.changed() and not stack._rows_cache.held()
     w.mark()
     m.eval()
     assert not w.changed()
