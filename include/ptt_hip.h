@@ -725,7 +725,9 @@ int ptt_rows_gemm_pool_f32(const float* X, int rows, int K, int ldx, const float
 int ptt_pool_select_f32(const float* pmax, const float* pmin, const int32_t* amax, const int32_t* amin, const float* act_scale,
                         const float* act_shift, int G, int C, float* out, int32_t* arg, ptt_stream_t stream);
 /* out[c] = sum over the R rows of X[r][c] — the bias gradient of a row-wise layer (nn.Linear / Conv1d(k=1) backward,
- * transformer_block/variants.py:154-164 in training) — in a fixed order: bit-reproducible. C % 4 == 0, 16-byte aligned rows. */
+ * transformer_block/variants.py:154-164 in training) — in a fixed order: bit-reproducible. Any C and ldx >= C: float4 loads where
+ * C % 4 == 0, ldx % 4 == 0 and X and the partials' destination (the workspace; `out` itself when R fits one chunk) are 16-byte
+ * aligned, scalar loads otherwise (the 259-channel vote layer, row views at an odd offset). */
 size_t ptt_colsum_workspace(int R, int C);
 int ptt_colsum_f32(const float* X, int R, int C, int ldx, float* out, void* workspace, size_t workspace_bytes, ptt_stream_t stream);
 size_t ptt_linear_wgrad_workspace(int R, int Cout, int Cin);

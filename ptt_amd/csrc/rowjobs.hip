@@ -420,6 +420,10 @@ extern "C" int ptt_row_jobs_f32(const ptt_row_job* jobs, int n_jobs, ptt_stream_
             if (j.out_split < 0 || j.out_split > j.Cout || (j.out_split > 0 && !j.out2) || j.res_split < 0 || j.res_split > j.Cout ||
                 j.act < 0 || j.act > 2)
                 return fail(PTT_EINVAL, "ptt_row_jobs_f32: job %d: out_split=%d res_split=%d act=%d", i, j.out_split, j.res_split, j.act);
+            if (j.out_col0 < 0 || j.ldo < j.out_col0 + j.Cout - j.out_split || (j.out_split > 0 && j.ldo2 < j.out_split) ||
+                (j.res && j.ldr < j.Cout - j.res_split) || (j.res2 && j.res_split > 0 && j.ldr2 < j.res_split) || (j.raw && j.ldraw < j.Cout))
+                return fail(PTT_EINVAL, "ptt_row_jobs_f32: job %d: ldo=%d ldo2=%d ldr=%d ldr2=%d ldraw=%d for Cout=%d out_split=%d out_col0=%d res_split=%d",
+                            i, j.ldo, j.ldo2, j.ldr, j.ldr2, j.ldraw, j.Cout, j.out_split, j.out_col0, j.res_split);
         } else return fail(PTT_EINVAL, "ptt_row_jobs_f32: job %d: epilogue %d", i, j.epilogue);
         RowJobDev& D = P.j[P.n];
         D.j = j;

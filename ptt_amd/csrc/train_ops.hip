@@ -1597,7 +1597,7 @@ extern "C" int ptt_bn_stats_f32(const float* X, int R, int C, int ldx, float eps
 
 extern "C" int ptt_bn_apply_f32(const float* Z, int ldz, const float* mean, const float* invstd, const float* gamma,
                                 const float* beta, int R, int C, int relu, float* X, int ldx, ptt_stream_t stream) {
-    if (R <= 0 || C <= 0) return fail(PTT_EINVAL, "ptt_bn_apply_f32: R=%d C=%d", R, C);
+    if (R <= 0 || C <= 0 || ldz < C || ldx < C) return fail(PTT_EINVAL, "ptt_bn_apply_f32: R=%d C=%d ldz=%d ldx=%d", R, C, ldz, ldx);
     if (!Z || !mean || !invstd || !gamma || !beta || !X) return fail(PTT_EINVAL, "ptt_bn_apply_f32: null pointer");
     if (vec4_ok(Z, ldz, C) && vec4_ok(X, ldx, C) && vec4_ok(mean, 4, 4) && vec4_ok(invstd, 4, 4) && vec4_ok(gamma, 4, 4) &&
         vec4_ok(beta, 4, 4)) {
@@ -1617,7 +1617,8 @@ extern "C" int ptt_bn_bwd_f32(const float* G, int ldg, const float* Act, int lda
                               const float* invstd, const float* gamma, int R, int C, int relu, float* dZ, int ldd,
                               float* dgamma, float* dbeta, void* ws, size_t ws_bytes, const float* act_scale,
                               const float* act_shift, ptt_stream_t stream) {
-    if (R <= 0 || C <= 0) return fail(PTT_EINVAL, "ptt_bn_bwd_f32: R=%d C=%d", R, C);
+    if (R <= 0 || C <= 0 || ldg < C || (Act && lda < C) || ldz < C || ldd < C)
+        return fail(PTT_EINVAL, "ptt_bn_bwd_f32: R=%d C=%d ldg=%d lda=%d ldz=%d ldd=%d", R, C, ldg, lda, ldz, ldd);
     if (!G || !Z || !mean || !invstd || !gamma || !dZ || !dgamma || !dbeta || (relu && !Act && !(act_scale && act_shift)))
         return fail(PTT_EINVAL, "ptt_bn_bwd_f32: null pointer");
     if (!ws || ws_bytes < ptt_bn_stats_workspace(R, C)) return fail(PTT_EWORKSPACE, "ptt_bn_bwd_f32: workspace too small");
@@ -1681,7 +1682,8 @@ extern "C" int ptt_bn_finish_f64(const double* sums, int C, float eps, float* me
 extern "C" int ptt_bn_bwd_sums_f64(const float* G, int ldg, const float* Act, int lda, const float* Z, int ldz, const float* mean,
                                    const float* invstd, int R, int C, double* sums, void* ws, size_t ws_bytes,
                                    const float* act_scale, const float* act_shift, ptt_stream_t stream) {
-    if (R <= 0 || C <= 0) return fail(PTT_EINVAL, "ptt_bn_bwd_sums_f64: R=%d C=%d", R, C);
+    if (R <= 0 || C <= 0 || ldg < C || (Act && lda < C) || ldz < C)
+        return fail(PTT_EINVAL, "ptt_bn_bwd_sums_f64: R=%d C=%d ldg=%d lda=%d ldz=%d", R, C, ldg, lda, ldz);
     if (!G || !Z || !mean || !invstd || !sums || (!Act && !(act_scale && act_shift)))
         return fail(PTT_EINVAL, "ptt_bn_bwd_sums_f64: null pointer");
     if (!ws || ws_bytes < ptt_bn_stats_workspace(R, C)) return fail(PTT_EWORKSPACE, "ptt_bn_bwd_sums_f64: workspace too small");
@@ -1700,7 +1702,8 @@ extern "C" int ptt_bn_bwd_apply_f32(const float* G, int ldg, const float* Act, i
                                     const float* invstd, const float* gamma, const float* sum_dy, const float* sum_dy_xhat,
                                     const double* count, int R, int C, float* dZ, int ldd, const float* act_scale,
                                     const float* act_shift, ptt_stream_t stream) {
-    if (R <= 0 || C <= 0) return fail(PTT_EINVAL, "ptt_bn_bwd_apply_f32: R=%d C=%d", R, C);
+    if (R <= 0 || C <= 0 || ldg < C || (Act && lda < C) || ldz < C || ldd < C)
+        return fail(PTT_EINVAL, "ptt_bn_bwd_apply_f32: R=%d C=%d ldg=%d lda=%d ldz=%d ldd=%d", R, C, ldg, lda, ldz, ldd);
     if (!G || !Z || !mean || !invstd || !gamma || !sum_dy || !sum_dy_xhat || !count || !dZ || (!Act && !(act_scale && act_shift)))
         return fail(PTT_EINVAL, "ptt_bn_bwd_apply_f32: null pointer");
     if (!(vec4_ok(G, ldg, C) && (Act ? vec4_ok(Act, lda, C) : (vec4_ok(act_scale, 4, 4) && vec4_ok(act_shift, 4, 4))) &&
@@ -1780,7 +1783,7 @@ extern "C" int ptt_bn_bwd_pooled_apply_f32(const float* dPooled, int ldp, const 
 
 extern "C" int ptt_pool_rows_f32(const float* X, int ldx, int G, int ns, int C, float* out, int ldo, int32_t* arg,
                                  const float* act_scale, const float* act_shift, ptt_stream_t stream) {
-    if (G <= 0 || ns <= 0 || C <= 0) return fail(PTT_EINVAL, "ptt_pool_rows_f32: G=%d ns=%d C=%d", G, ns, C);
+    if (G <= 0 || ns <= 0 || C <= 0 || ldx < C || ldo < C) return fail(PTT_EINVAL, "ptt_pool_rows_f32: G=%d ns=%d C=%d ldx=%d ldo=%d", G, ns, C, ldx, ldo);
     if (!X || !out || !arg) return fail(PTT_EINVAL, "ptt_pool_rows_f32: null pointer");
     hipLaunchKernelGGL(pool_rows_kernel, dim3(ew_grid((size_t)G * C)), dim3(256), 0, as_stream(stream), X, ldx, G, ns, C, out, ldo, arg,
                        act_scale, act_scale ? act_shift : nullptr);
@@ -1798,7 +1801,8 @@ extern "C" int ptt_pool_select_f32(const float* pmax, const float* pmin, const i
 
 extern "C" int ptt_pool_rows_bwd_f32(const float* dOut, int ldo, const int32_t* arg, int G, int ns, int C, float* dX, int ldx,
                                      ptt_stream_t stream) {
-    if (G <= 0 || ns <= 0 || C <= 0) return fail(PTT_EINVAL, "ptt_pool_rows_bwd_f32: G=%d ns=%d C=%d", G, ns, C);
+    if (G <= 0 || ns <= 0 || C <= 0 || ldo < C || ldx < C)
+        return fail(PTT_EINVAL, "ptt_pool_rows_bwd_f32: G=%d ns=%d C=%d ldo=%d ldx=%d", G, ns, C, ldo, ldx);
     if (!dOut || !arg || !dX) return fail(PTT_EINVAL, "ptt_pool_rows_bwd_f32: null pointer");
     hipLaunchKernelGGL(pool_rows_bwd_kernel, dim3(ew_grid((size_t)G * ns * C)), dim3(256), 0, as_stream(stream), dOut, ldo, arg, G, ns,
                        C, dX, ldx);
@@ -1998,8 +2002,10 @@ extern "C" int ptt_colsum_partials_f32(const float* X, int R, int C, int ldx, vo
 
 extern "C" size_t ptt_linear_wgrad_workspace(int R, int Cout, int Cin) {
     if (R <= 0 || Cout <= 0 || Cin <= 0) return 0;
-    if (wgrad_smallk_ok(Cout, Cin)) return (size_t)((R + WK_ROWS - 1) / WK_ROWS) * (size_t)Cout * Cin * sizeof(float);
-    const int rows = wgrad_stream_ok(R, Cout, Cin, Cout, Cin) ? wgrad_stream_rows(R) : wgrad_chunk_rows(R, Cout, Cin);   // the finer chunking
+    int rows = wgrad_stream_ok(R, Cout, Cin, Cout, Cin) ? wgrad_stream_rows(R) : wgrad_chunk_rows(R, Cout, Cin);   // the finer chunking
+    // a small-K shape takes the small-K kernel only with float4-addressable dZ and no input transform; otherwise the block kernel,
+    // whose chunks may be shorter: room for whichever writes more partials
+    if (wgrad_smallk_ok(Cout, Cin) && WK_ROWS < rows) rows = WK_ROWS;
     return (size_t)((R + rows - 1) / rows) * (size_t)Cout * Cin * sizeof(float);
 }
 
