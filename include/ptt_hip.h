@@ -180,7 +180,7 @@ typedef struct ptt_sa_layer {
     const float* scale;   /* (Cout) gamma/sqrt(var+eps), or NULL = 1                   */
     const float* shift;   /* (Cout) beta - mean*scale (or conv bias), or NULL = 0      */
     int Cin;              /* input channels of this layer (first layer: 3*use_xyz + C) */
-    int Cout;             /* multiple of 32                                            */
+    int Cout;             /* multiple of 32, <= 256 (PTT_EUNSUPPORTED otherwise)       */
     int relu;
 } ptt_sa_layer;
 
@@ -300,7 +300,7 @@ typedef struct ptt_sa_desc {
     int64_t feat_sb, feat_sc, feat_sn; /* element strides of feat[b][c][n]             */
     float* out;           /* pooled features                                           */
     int64_t out_sb, out_sc, out_sm;    /* element strides of out[b][c][m]              */
-    int B, N, M, nsample, C;
+    int B, N, M, nsample, C;           /* nsample 16, 32 or 64 (PTT_EUNSUPPORTED otherwise) */
     float radius;
     int use_xyz;          /* prepend the 3 relative coordinates (reference default)    */
     int normalize_xyz;    /* divide them by radius (pointnet2_utils.py:353-354)        */
@@ -350,7 +350,7 @@ size_t ptt_sa_compact_workspace(int B, int M);
  *   out[b,:,j] = max_i SharedMLP(fusion)[b,:,i,j]
  * Layer 0 is split: W0.fusion = w_sim*cos_ij + P[b,i,:], with P = W0[:,1:].[xyz_i;feat_i] computed
  * once per template point by ptt_linear_f32. `layers` are the REMAINING SharedMLP layers.
- * The template seeds are walked in chunks of 64 with a running max (Nt % 64 == 0); the cosine map comes from
+ * The template seeds are walked in chunks of 64 with a running max (Nt % 64 == 0, PTT_EUNSUPPORTED otherwise); the cosine map comes from
  * ptt_cosine_map_f32 (below).
  * ------------------------------------------------------------------------------- */
 typedef struct ptt_xcorr_desc {
@@ -372,7 +372,8 @@ typedef struct ptt_xcorr_desc {
      * cosines inside the kernel (cos_t is not read, ptt_cosine_map_f32 not needed). Half h writes its maxima to
      * out + h * out_sh (same strides); the maximum over the template axis is the element-wise maximum of the two, taken by
      * the consumer (ptt_row_job.Xmax). search_feat[b][j][:], templ_feat[b][i][:] with unit channel stride, element strides
-     * s_sb / s_sn / t_sb / t_sn, C channels (C % 4 == 0), eps of F.cosine_similarity; B * Ns % 8 == 0; sim_out NULL. */
+     * s_sb / s_sn / t_sb / t_sn, C channels (C % 4 == 0), eps of F.cosine_similarity; B * Ns % 8 == 0; sim_out NULL
+     * (PTT_EINVAL otherwise). */
     int32_t split; int64_t out_sh;
     const float* search_feat; const float* templ_feat;
     int64_t s_sb, s_sn, t_sb, t_sn;
@@ -393,7 +394,8 @@ int ptt_cosine_map_f32(const float* search_feat, int64_t s_sb, int64_t s_sn, int
  *   attn = softmax_j(a / sqrt(D));    res_i = sum_j attn * (v_j + delta)
  * replaces TransformerBlock.forward lines                  variants.py:158-163
  *   qkv (B,N,3*D) = [q | k | v] rows (from ptt_linear_f32 with the stacked weight),
- *   knn (B,N,k) i32. D = 512 and k = 16 are the instantiated configuration.
+ *   knn (B,N,k) i32. D = 512 and k = 16 are the instantiated configuration; N must be even (a tile holds two points of
+ *   one cloud; PTT_EUNSUPPORTED otherwise).
  *   res (B,N,D); attn (B,N,k,D) or NULL (the heads discard it: centroids_voting_head.py:76).
  * ------------------------------------------------------------------------------- */
 typedef struct ptt_attn_desc {

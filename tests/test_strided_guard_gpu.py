@@ -16,8 +16,8 @@ should run. A refused launch must leave every output word untouched.
 What this does not prove: a read past an input that does not influence the result goes unseen. NaN surroundings catch leaks
 (a staged row too many times a zero weight is NaN), not every stray load. Nothing here measures speed.
 
-Out of scope (issue): the index ops (no leading dimensions; covered against the oracle) and the fused SA / xcorr / pair kernels
-(their descriptors take whole tensors)."""
+Out of scope here: the index ops (no leading dimensions) are behind guard bands in tests/test_index_guard_gpu.py, the fused
+SA / xcorr / pair kernels (their descriptors take whole tensors and output strides) in tests/test_fused_guard_gpu.py."""
 import ctypes
 
 import numpy as np
