@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 28
+#define PTT_ABI_VERSION 29
 
 enum {
     PTT_OK = 0,
@@ -67,6 +67,30 @@ int ptt_fps_f32(const float* xyz, int B, int N, int npoint, int32_t* idx_out,
  * N > 16384 or npoint > 15360): the running min-distance in `workspace` (>= B*N floats), identical picks, slower. */
 int ptt_fps_ws_f32(const float* xyz, int B, int N, int npoint, int32_t* idx_out, float* workspace,
                    size_t workspace_elems, ptt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * F1b (ABI 29)  feature-space furthest point sampling (3DSSD's F-FPS)
+ * stands in for _ext.furthest_point_sampling_with_dist(square_distance(cat, cat), npoint) of sample_method 'ffps'
+ * (pointnet2_modules.py:64-67, cat = [xyz ; features] per point), which the reference's extension never provided —
+ * without the (B,N,N) matrix or the (B,N,N,C+3) intermediate it is the sum of: the distances are formed on the fly.
+ *   xyz (B,N,3) f32 contiguous; feat: element [b,c,k] at feat[b*feat_sb + c*feat_sc + k*feat_sn] (element strides: a (B,C,N)
+ *   tensor, the point-major (B,N,C) rows of the fused path and rows with a padded stride are all read in place)
+ *   -> idx_out (B,npoint) i32
+ * With v_k = [x_k, y_k, z_k, f_0k, ..., f_(C-1)k] and D = C + 3: d(i,k) is an fp32 accumulator that starts at 0 and takes, for
+ * c = 0 .. D-1 in this order, t = v_i[c] - v_k[c]; acc = acc + t*t — every operation rounded on its own, no FMA contraction.
+ * tmp[:] = 1e10, idx[0] = 0; for j = 1 .. npoint-1: tmp[k] = min(tmp[k], d(idx[j-1], k)) for every k, idx[j] = the lowest
+ * k that attains max tmp. No origin-ball skip (that is ptt_fps_f32's, inherited from the coordinate op): with C == 0
+ * (feat may be NULL) the picks are those of this definition, not ptt_fps_f32's. A cloud of identical points gives zeros.
+ * Non-finite input is outside the contract; no index leaves [0, N) even then.
+ * Limits (PTT_EUNSUPPORTED beyond them): N <= 16384, C <= 1024, npoint <= 15360 (npoint > N is allowed), and one cloud's
+ * features within 2^31 elements: (N-1)*|feat_sn| + (C-1)*|feat_sc| <= INT_MAX. Null xyz / idx_out (feat with C > 0) or
+ * B, N, npoint < 1 or C < 0: PTT_EINVAL. Both are answered before any runtime call.
+ * One workgroup per cloud. C = 128 / 256 / 257 with N <= 512 / 256 / 256 (the model's levels): every point's vector stays in its
+ * thread's registers; any other shape streams the cloud's N x D values from L2 every iteration (coalesced when feat_sn == 1).
+ * Same picks either way. No workspace, no allocation, no host synchronisation, capturable.
+ * ------------------------------------------------------------------------------- */
+int ptt_ffps_f32(const float* xyz, const float* feat, int64_t feat_sb, int64_t feat_sc, int64_t feat_sn,
+                 int B, int N, int C, int npoint, int32_t* idx_out, ptt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * F2  gather centres

@@ -39,6 +39,7 @@ struct DevSwitches {
     int fps_plain = 0;                   // PTT_FPS_PLAIN=1: coordinates carried through the selects for every cloud size
     int ball_cpw = 0;                    // PTT_BALL_CPW=1|4: centres per wave of the ball-query kernels (0: by launch size)
     int fps_t = 0;                       // PTT_FPS_T: FPS threads per cloud at N <= 2048
+    int ffps_stream = 0;                 // PTT_FFPS_STREAM=1: ptt_ffps_f32 streams the features at every shape (no resident form)
     int group_grad_global = 0;           // PTT_GROUP_GRAD_GLOBAL: global atomics in ptt_group_grad_f32
     long long* stamps = nullptr;         // PTT_DEBUG_STAMPS=<hex device pointer> (PTT_DEV builds only)
 };

@@ -45,6 +45,7 @@ static DevSwitches read_switches() {
     if (const char* e = getenv("PTT_FPS_PLAIN")) d.fps_plain = atoi(e);
     if (const char* e = getenv("PTT_SA_LDS_CHUNK")) d.sa_lds_chunk = atoi(e);
     if (const char* e = getenv("PTT_FPS_T")) d.fps_t = atoi(e);
+    if (const char* e = getenv("PTT_FFPS_STREAM")) d.ffps_stream = atoi(e);
     if (getenv("PTT_GROUP_GRAD_GLOBAL")) d.group_grad_global = 1;
     if (const char* e = getenv("PTT_DEBUG_STAMPS")) d.stamps = reinterpret_cast<long long*>(strtoull(e, nullptr, 16));
     return d;

@@ -897,6 +897,173 @@ __global__ __launch_bounds__(1024) void fps_ws_kernel(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Feature-space FPS (3DSSD's F-FPS; the 'ffps' branch of pointnet2_modules.py:64-67): furthest point sampling on the
+// D = 3 + C vectors v_k = [xyz_k ; feat_k], matrix-free. fps_kernel's skeleton — one workgroup per cloud, the running minima
+// in registers, the picks collected in LDS and stored once, lowest index wins — with two differences:
+//   * a point's vector does not fit registers beside its minimum for every C, so it is streamed from L2 every iteration.
+//     Thread t owns the STRIDED points t, t + T, ...: with features stored (B,C,N) a wave's loads of one channel are one
+//     coalesced line. Lower lanes then no longer hold lower indices, so the arg-max is a (distance, index) pair — larger
+//     distance, then lower index — through the wave (two DPP reductions) and through one LDS slot per wave;
+//   * every thread needs the winner's whole vector: the workgroup copies it into LDS once per iteration (each channel
+//     then is one broadcast LDS read per thread), which costs the iteration a second barrier.
+// CR > 0 is the resident form for the model's shapes (C = CR known at compile time, one point per thread): the point's vector is
+// loaded once into registers — through the same strides, so any layout — and the winner writes its own registers to LDS. The
+// streamed form is bound by what one workgroup reads from L2 (268 KB per iteration at SA1: 4.1 us); the resident one by the
+// chain of D dependent adds the summation order prescribes ("Feature-space FPS").
+// d(i,k) = sum over c = 0 .. D-1, in this order, of (v_i[c] - v_k[c])^2, every operation rounded on its own (this file is
+// compiled without FMA contraction). No origin-ball skip: that is a quirk of the coordinate op. Padding lanes carry the
+// minimum -1 and never win; a non-finite distance leaves a minimum as it is (fminf), so no index leaves [0, N).
+// The picks are below 65536 (N <= 16384): 2 bytes each in LDS, which leaves room for the winner's vector at every size.
+// ------------------------------------------------------------------------------------------
+// (Clouds above 8192 points, 16 per thread at 128 registers, spill about a hundred of them: right, and slow. No config comes near.)
+constexpr int FFPS_MAX_N = 16384, FFPS_MAX_C = 1024, FFPS_MAX_NPOINT = 15360;
+#define FFPS_WIN(C) ((4 + (C) + 3) & ~3)                                // floats of LDS for the winner's vector
+
+template <int T, int P, int CR>
+__global__ __launch_bounds__(T) void ffps_kernel(const float* __restrict__ xyz, const float* __restrict__ feat, long long feat_sb,
+                                                long long feat_sc, long long feat_sn, int N, int C, int npoint,
+                                                int32_t* __restrict__ idx_out) {
+    constexpr int W = T / 64;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const float* __restrict__ pts = xyz + (size_t)b * N * 3;
+    const float* __restrict__ fb = feat + (long long)b * feat_sb;       // never dereferenced when C == 0
+    int32_t* __restrict__ out = idx_out + (size_t)b * npoint;
+
+    extern __shared__ __attribute__((aligned(16))) float ffps_lds[];    // the winner's vector: xyz at [0, 3), channel c at [4 + c]
+    float* win = ffps_lds;                                              // (16-byte aligned); then npoint uint16 picks
+    unsigned short* sel = reinterpret_cast<unsigned short*>(ffps_lds + FFPS_WIN(C));
+    __shared__ float slot_v[W];
+    __shared__ int slot_i[W];
+
+    constexpr int PH = P > 8 ? 8 : P;                                   // points per pass over the channels
+    constexpr int UC = P >= 8 ? 2 : 8;                                  // channels unrolled: 8 to 16 loads in flight per thread
+    float px[P], py[P], pz[P], md[P];
+    // a point's offset from the cloud's lowest point address: unsigned 32 bits (the entry point checks the span), so that a
+    // load is a scalar base (the channel) + a vector offset
+    unsigned off[P];
+    const float* __restrict__ f0 = fb + (feat_sn < 0 ? (long long)(N - 1) * feat_sn : 0);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const int k = i * T + t;
+        const int kk = k < N ? k : N - 1;                               // padding lanes read a real point and ignore it
+        px[i] = pts[3 * kk + 0]; py[i] = pts[3 * kk + 1]; pz[i] = pts[3 * kk + 2];
+        md[i] = k < N ? 1e10f : -1.0f;
+        off[i] = (unsigned)((long long)(feat_sn < 0 ? kk - (N - 1) : kk) * feat_sn);
+    }
+    static_assert(CR == 0 || P == 1, "the resident form holds one point per thread");
+    float v[CR > 0 ? CR : 1];
+    if constexpr (CR > 0) {
+#pragma unroll
+        for (int c = 0; c < CR; ++c) v[c] = f0[(long long)c * feat_sc + off[0]];
+    }
+    if (t == 0) sel[0] = 0;
+    int last = 0;
+    for (int j = 1; j < npoint; ++j) {
+        // (the barrier that closed the previous iteration's exchange also ordered its reads of `win` before these writes)
+        if constexpr (CR > 0) {                                         // resident: the winner's vector is in the winner's registers
+            if (t == last) {
+                win[0] = px[0]; win[1] = py[0]; win[2] = pz[0];
+#pragma unroll
+                for (int c = 0; c < CR; ++c) win[4 + c] = v[c];
+            }
+        } else {
+            for (int c = t; c < 4 + C; c += T)
+                if (c != 3) win[c] = c < 3 ? pts[3 * last + c] : fb[(long long)(c - 4) * feat_sc + (long long)last * feat_sn];
+        }
+        __syncthreads();
+        const float wx = win[0], wy = win[1], wz = win[2];
+        float best = -1.0f;
+        int besti = 0;
+#pragma unroll
+        for (int h = 0; h < P; h += PH) {
+            float acc[PH];
+#pragma unroll
+            for (int i = 0; i < PH; ++i) {
+                const float dx = wx - px[h + i], dy = wy - py[h + i], dz = wz - pz[h + i];
+                acc[i] = (dx * dx + dy * dy) + dz * dz;                 // = ((0 + dx*dx) + dy*dy) + dz*dz
+            }
+            if constexpr (CR > 0) {                                     // resident: the thread's one point never leaves its registers
+#pragma unroll
+                for (int c = 0; c + 1 < CR; c += 2) {
+                    const fps_f2 d = fps_f2{win[4 + c], win[4 + c + 1]} - fps_f2{v[c], v[c + 1]};
+                    const fps_f2 q = d * d;
+                    acc[0] = acc[0] + q[0];
+                    acc[0] = acc[0] + q[1];
+                }
+                if constexpr (CR & 1) {
+                    const float d = win[4 + CR - 1] - v[CR - 1];
+                    acc[0] = acc[0] + d * d;
+                }
+            } else {
+                const float* __restrict__ fc = f0;
+#pragma unroll UC
+                for (int c = 0; c < C; ++c, fc += feat_sc) {
+                    const float w = win[4 + c];
+#pragma unroll
+                    for (int i = 0; i < PH; ++i) {
+                        const float d = w - fc[off[h + i]];
+                        acc[i] = acc[i] + d * d;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < PH; ++i) {
+                const float m = md[h + i] < 0.f ? -1.0f : fminf(md[h + i], acc[i]);
+                md[h + i] = m;
+                const bool take = m > best;                             // strict: ascending i is ascending index
+                best = take ? m : best;
+                besti = take ? (h + i) * T + t : besti;
+            }
+        }
+        // the wave's arg-max on DPP, no LDS: the maximum, then the lowest index that attains it (one point per thread: the lowest
+        // lane — a ballot; else a second reduction over the indices of the lanes at the maximum). `best` is never NaN.
+        const float wmax = wave_max_f32_fused(best);
+        int widx;
+        if constexpr (P == 1) widx = wv * 64 + __ffsll((long long)__ballot(best == wmax)) - 1;
+        else widx = wave_min_i32(best == wmax ? besti : INT_MAX);
+        if (lane == 0) { slot_v[wv] = wmax; slot_i[wv] = widx; }
+        __syncthreads();
+        float gd = slot_v[0];
+        int gi = slot_i[0];
+#pragma unroll
+        for (int w = 1; w < W; ++w) {                                   // branch-free: larger distance, then lower index
+            const float sv = slot_v[w];
+            const int si = slot_i[w];
+            const bool take = sv > gd || (sv == gd && si < gi);
+            gd = take ? sv : gd;
+            gi = take ? si : gi;
+        }
+        last = __builtin_amdgcn_readfirstlane(gi);
+        if (t == 0) sel[j] = (unsigned short)last;
+    }
+    __syncthreads();
+    for (int j = t; j < npoint; j += T) out[j] = sel[j];
+}
+
+template <int T, int P, int CR = 0>
+static int launch_ffps(const float* xyz, const float* feat, long long sb, long long sc, long long sn, int B, int N, int C, int npoint,
+                       int32_t* idx, hipStream_t s) {
+    const size_t lds = (size_t)FFPS_WIN(C) * sizeof(float) + (size_t)((npoint + 1) & ~1) * sizeof(unsigned short);   // <= 34.1 KB
+    hipLaunchKernelGGL((ffps_kernel<T, P, CR>), dim3(B), dim3(T), lds, s, xyz, feat, sb, sc, sn, N, C, npoint, idx);
+    return check_launch(CR ? "ffps_kernel(resident)" : "ffps_kernel");
+}
+
+// The resident form for the channel counts the model runs (C = 128: SA1 and the template's SA2; 256: SA2; 257: the box head) at
+// one point per thread: C = 128 up to 512 points (131 values beside 2 waves per SIMD), 256 / 257 up to 256 points (one wave per SIMD
+// owns 512 registers). -1: not such a shape.
+template <int CR>
+static int launch_ffps_resident(const float* xyz, const float* feat, long long sb, long long sc, long long sn, int B, int N, int npoint,
+                                int32_t* idx, hipStream_t s) {
+    if (N <= 64) return launch_ffps<64, 1, CR>(xyz, feat, sb, sc, sn, B, N, CR, npoint, idx, s);
+    if (N <= 128) return launch_ffps<128, 1, CR>(xyz, feat, sb, sc, sn, B, N, CR, npoint, idx, s);
+    if (N <= 256) return launch_ffps<256, 1, CR>(xyz, feat, sb, sc, sn, B, N, CR, npoint, idx, s);
+    if constexpr (CR <= 128) {
+        if (N <= 512) return launch_ffps<512, 1, CR>(xyz, feat, sb, sc, sn, B, N, CR, npoint, idx, s);
+    }
+    return -1;
+}
+
 // A spatial processing order for the points of every cloud: Morton keys (10 bits per axis inside the cloud's bounding box) sorted
 // in LDS (bitonic, one workgroup per cloud). The Point-Transformer pair kernel gives a workgroup two points and gathers the k | v
 // rows of their 32 neighbours: in sampling order (furthest point sampling = as far apart as possible) consecutive workgroups
@@ -1215,6 +1382,39 @@ extern "C" int ptt_fps_ws_f32(const float* xyz, int B, int N, int npoint, int32_
         return fail(PTT_EWORKSPACE, "ptt_fps_ws_f32: %zu floats of workspace needed", (size_t)B * N);
     hipLaunchKernelGGL(fps_ws_kernel, dim3(B), dim3(1024), 0, as_stream(stream), xyz, N, npoint, workspace, idx_out);
     return check_launch("fps_ws_kernel");
+}
+
+extern "C" int ptt_ffps_f32(const float* xyz, const float* feat, int64_t feat_sb, int64_t feat_sc, int64_t feat_sn, int B, int N, int C,
+                            int npoint, int32_t* idx_out, ptt_stream_t stream) {
+    if (B < 1 || N < 1 || npoint < 1 || C < 0) return fail(PTT_EINVAL, "ptt_ffps_f32: B=%d N=%d C=%d npoint=%d", B, N, C, npoint);
+    if (!xyz || !idx_out || (C > 0 && !feat)) return fail(PTT_EINVAL, "ptt_ffps_f32: null pointer");
+    if (N > FFPS_MAX_N || C > FFPS_MAX_C || npoint > FFPS_MAX_NPOINT)
+        return fail(PTT_EUNSUPPORTED, "ptt_ffps_f32: N=%d C=%d npoint=%d exceed the limits N <= %d, C <= %d, npoint <= %d", N, C, npoint,
+                    FFPS_MAX_N, FFPS_MAX_C, FFPS_MAX_NPOINT);
+    if (C > 0 && (long long)(N - 1) * llabs((long long)feat_sn) + (long long)(C - 1) * llabs((long long)feat_sc) > INT_MAX)
+        return fail(PTT_EUNSUPPORTED, "ptt_ffps_f32: one cloud's features span more than 2^31 elements (strides %lld, %lld)",
+                    (long long)feat_sc, (long long)feat_sn);
+    hipStream_t s = as_stream(stream);
+    if (C == 0) { feat = xyz; feat_sb = feat_sc = feat_sn = 0; }          // never read
+    // T = the cloud's size up to 1024: the iteration is C dependent-free L2 loads per point, and it is waves that hide them
+    if (!dev_switches().ffps_stream) {
+        int rc = -1;
+        if (C == 128) rc = launch_ffps_resident<128>(xyz, feat, feat_sb, feat_sc, feat_sn, B, N, npoint, idx_out, s);
+        else if (C == 256) rc = launch_ffps_resident<256>(xyz, feat, feat_sb, feat_sc, feat_sn, B, N, npoint, idx_out, s);
+        else if (C == 257) rc = launch_ffps_resident<257>(xyz, feat, feat_sb, feat_sc, feat_sn, B, N, npoint, idx_out, s);
+        if (rc != -1) return rc;
+    }
+#define PTT_FFPS_CASE(T, P) return launch_ffps<T, P>(xyz, feat, feat_sb, feat_sc, feat_sn, B, N, C, npoint, idx_out, s)
+    if (N <= 64) PTT_FFPS_CASE(64, 1);
+    if (N <= 128) PTT_FFPS_CASE(128, 1);
+    if (N <= 256) PTT_FFPS_CASE(256, 1);
+    if (N <= 512) PTT_FFPS_CASE(512, 1);
+    if (N <= 1024) PTT_FFPS_CASE(1024, 1);
+    if (N <= 2048) PTT_FFPS_CASE(1024, 2);
+    if (N <= 4096) PTT_FFPS_CASE(1024, 4);
+    if (N <= 8192) PTT_FFPS_CASE(1024, 8);
+    PTT_FFPS_CASE(1024, 16);
+#undef PTT_FFPS_CASE
 }
 
 // centres per wave of the ball-query kernels: 4 when the launch still has at least two waves per SIMD of the device and

@@ -75,8 +75,12 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
         if self.sample_method in ('rs', 'sequence'):
             return index_table(xyz.size(0), npoint, xyz.device, torch.int32)
         if self.sample_method == 'ffps':
-            raise NotImplementedError("sample_method 'ffps' needs furthest_point_sampling_with_dist, which the "
-                                      "reference's extension never provided (tools/cfgs/kitti_models/ptt.yaml:42)")
+            # furthest points in [xyz ; features] space (reference :64-67, a branch its extension could never run: it has no
+            # furthest_point_sampling_with_dist) — matrix-free, the features read in place whatever their layout
+            if features is None:
+                raise ValueError("sample_method 'ffps': a level without point features cannot sample in feature space "
+                                 "(use 'fps' for it)")
+            return ops.feature_fps(xyz.contiguous(), features.detach(), npoint)
         raise NotImplementedError(self.sample_method)
 
     # ------------------------------------------------------------------ fused-path parameters

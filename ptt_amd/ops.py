@@ -205,6 +205,46 @@ def furthest_point_sampling(xyz, npoint):
     return out
 
 
+FFPS_MAX_N, FFPS_MAX_C, FFPS_MAX_NPOINT = 16384, 1024, 15360            # ptt_ffps_f32's limits (include/ptt_hip.h)
+
+
+def feature_fps(xyz, features, npoint):
+    """Feature-space furthest point sampling (sample_method 'ffps', 3DSSD's F-FPS): xyz (B,N,3) f32 contiguous, features (B,C,N)
+    f32 with ANY strides (read in place through .stride(): the (B,C,N) tensors of the reference, the transposed view of the fused
+    path's point-major rows, rows with a padded stride) or None -> (B,npoint) i32. Stands in for
+    _ext.furthest_point_sampling_with_dist(square_distance(cat([xyz ; features])), npoint) (pointnet2_modules.py:64-67) without
+    the (B,N,N) matrix; the summation order of a distance is fixed (coordinates first, then the channels in order:
+    include/ptt_hip.h). Sizes beyond the kernel's limits raise ValueError."""
+    _chk(xyz, "xyz", torch.float32, 3)
+    B, N, _ = xyz.shape
+    C = 0
+    if features is not None:
+        if not isinstance(features, torch.Tensor):
+            raise TypeError("features must be a torch.Tensor")
+        if not features.is_cuda:
+            raise RuntimeError("features must be a device (HIP) tensor — CPU tensors are not supported")
+        if features.dtype != torch.float32:
+            raise RuntimeError("features must be torch.float32, got %s" % features.dtype)
+        if features.dim() != 3 or features.shape[0] != B or features.shape[2] != N:
+            raise RuntimeError("features must be (B,C,N) = (%d,C,%d), got %s" % (B, N, tuple(features.shape)))
+        C = features.shape[1]
+    npoint = int(npoint)
+    if N > FFPS_MAX_N or C > FFPS_MAX_C or npoint > FFPS_MAX_NPOINT:
+        raise ValueError("feature_fps: N=%d, C=%d, npoint=%d exceed the kernel's limits N <= %d, C <= %d, npoint <= %d"
+                         % (N, C, npoint, FFPS_MAX_N, FFPS_MAX_C, FFPS_MAX_NPOINT))
+    if N < 1 or npoint < 1:
+        raise ValueError("feature_fps: N=%d and npoint=%d must be at least 1" % (N, npoint))
+    out = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
+    if B == 0:
+        return out
+    sb, sc, sn = features.stride() if C else (0, 0, 0)
+    if C and (N - 1) * abs(sn) + (C - 1) * abs(sc) > 2 ** 31 - 1:
+        raise ValueError("feature_fps: one cloud's features span more than 2^31 - 1 elements (strides %d, %d)" % (sc, sn))
+    _launch("ptt_ffps_f32", xyz.device, _ptr(xyz), _ptr(features if C else None), sb, sc, sn, B, N, C, npoint, _ptr(out),
+            timed='ptt_ffps_f32')
+    return out
+
+
 def gather_points(features, idx):
     """(B,C,N) f32, (B,M) i32 -> (B,C,M).  Replaces _ext.gather_points (pointnet2_utils.py:112)."""
     _chk(features, "features", torch.float32, 3)
