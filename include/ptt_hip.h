@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 29
+#define PTT_ABI_VERSION 30
 
 enum {
     PTT_OK = 0,
@@ -498,6 +498,25 @@ int ptt_crop_compact_f32(const ptt_crop_job* jobs_device, int n_jobs, ptt_stream
  * of the launch costs more than the launch. The table is read before the call returns. */
 #define PTT_CROP_JOBS_BY_VALUE_MAX 8
 int ptt_crop_compact_host_f32(const ptt_crop_job* jobs_host, int n_jobs, ptt_stream_t stream);
+
+/* ptt_crop_scan_f32 (ABI 30) — the crops of ptt_crop_compact_f32 for clouds that are whole LiDAR scans (35k - 130k points, a few targets):
+ * every job is spread over the chip instead of walking its cloud on one workgroup. Same job table (DEVICE memory), same
+ * results bit for bit: the same survivors in their original order with the same float32 values (one shared per-point
+ * function), *count = their number even where it exceeds `capacity`, rows from `capacity` on not written.
+ *   Geometry: grid = (chunks of PTT_SCAN_CROP_CHUNK points of the longest cloud) x (jobs); a workgroup handles one chunk of one
+ *   job. Two launches: the first writes the survivor count of every (job, chunk) into the workspace, the second adds up the
+ *   counts of the chunks in front of it, repeats the test and writes its rows. No workgroup waits for another, nothing is
+ *   placed by an atomic: the result does not depend on scheduling, and a second call writes identical bytes.
+ *   max_points: the host's upper bound on every job's n_points; it sizes the grid. Chunks past a job's own n_points contribute
+ *   nothing; a job with n_points = 0 gives *count = 0. Points from max_points (rounded up to a whole chunk) on are NOT looked at:
+ *   the caller guarantees n_points <= max_points (the device cannot report a violation; ops.crop_scan checks the host table).
+ *   ws / ws_bytes: ptt_crop_scan_workspace(n_jobs, max_points) bytes of device memory (one int32 per job and chunk), 4-byte
+ *   aligned, overwritten by every call; less than that is PTT_EINVAL. n_jobs <= 65535.
+ *   Not supported: label_out != NULL and append != 0 — both fields are IGNORED here (no labels are written, rows start at 0).
+ *   Callers that hold the host table refuse such jobs before uploading (ops.crop_scan raises ValueError). */
+#define PTT_SCAN_CROP_CHUNK 1024
+size_t ptt_crop_scan_workspace(int n_jobs, int max_points);
+int ptt_crop_scan_f32(const ptt_crop_job* jobs_device, int n_jobs, int max_points, void* ws, size_t ws_bytes, ptt_stream_t stream);
 
 /* ptt_regularize_f32 — one job = regularize_pc(pc, input_size, istrain=False) (kitti_tracking_utils.py:342-367) on the
  * concatenation of up to PTT_MAX_SEGMENTS compacted crops (get_model :219-236 concatenates the crops of several

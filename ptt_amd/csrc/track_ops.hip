@@ -67,6 +67,40 @@ __device__ __forceinline__ int block_rank(bool flag, int* wsum, int& total) {
     return base + below;
 }
 
+// crop_center_pc's arithmetic for ONE point (x, y, z) of job j, shared by every crop kernel so that they round alike by
+// construction: -> whether the point survives both crops; (ox, oy, oz) = the point in the box frame (valid once it passed the
+// first crop); want_label (uniform over the workgroup): `label` = the point lies inside the ground-truth box.
+__device__ __forceinline__ bool crop_point(const ptt_crop_job& j, float x, float y, float z, bool want_label, float& ox, float& oy, float& oz,
+                                           bool& label) {
+    // crop_pc in the cloud's frame: float32 point against float64 bounds, strict on both sides
+    bool keep = (double)x > j.lo1[0] && (double)x < j.hi1[0] && (double)y > j.lo1[1] && (double)y < j.hi1[1] &&
+                (double)z > j.lo1[2] && (double)z < j.hi1[2];
+    if (keep && want_label) {
+        // get_label_by_box on the first crop: the same translate / rotate / strict test in the ground-truth box's frame
+        const double tx = (double)(float)((double)x + j.ltrans[0]);
+        const double ty = (double)(float)((double)y + j.ltrans[1]);
+        const double tz = (double)(float)((double)z + j.ltrans[2]);
+        const float lx = (float)fma(j.lrot[2], tz, fma(j.lrot[1], ty, j.lrot[0] * tx));
+        const float ly = (float)fma(j.lrot[5], tz, fma(j.lrot[4], ty, j.lrot[3] * tx));
+        const float lz = (float)fma(j.lrot[8], tz, fma(j.lrot[7], ty, j.lrot[6] * tx));
+        label = (double)lx > j.llo[0] && (double)lx < j.lhi[0] && (double)ly > j.llo[1] && (double)ly < j.lhi[1] &&
+                (double)lz > j.llo[2] && (double)lz < j.lhi[2];
+    }
+    if (keep) {
+        // PointCloud.translate: points[i,:] = points[i,:] + x[i] (float64 sum stored to the float32 array)
+        const double tx = (double)(float)((double)x + j.trans[0]);
+        const double ty = (double)(float)((double)y + j.trans[1]);
+        const double tz = (double)(float)((double)z + j.trans[2]);
+        // PointCloud.rotate: np.dot(rot (f64), points) stored to float32
+        ox = (float)fma(j.rot[2], tz, fma(j.rot[1], ty, j.rot[0] * tx));
+        oy = (float)fma(j.rot[5], tz, fma(j.rot[4], ty, j.rot[3] * tx));
+        oz = (float)fma(j.rot[8], tz, fma(j.rot[7], ty, j.rot[6] * tx));
+        keep = (double)ox > j.lo2[0] && (double)ox < j.hi2[0] && (double)oy > j.lo2[1] && (double)oy < j.hi2[1] &&
+               (double)oz > j.lo2[2] && (double)oz < j.hi2[2];
+    }
+    return keep;
+}
+
 // One workgroup per crop job: a stable stream compaction over the cloud in chunks of T points. An append job (a running
 // store of earlier crops, SHAPE_AGGREGATION = all) starts at the store's total instead of row 0.
 template <int T>
@@ -87,35 +121,7 @@ __device__ __forceinline__ void crop_compact_body(const ptt_crop_job& j) {
         const int i = base + (int)threadIdx.x;
         bool keep = false, label = false;
         float ox = 0.f, oy = 0.f, oz = 0.f;
-        if (i < j.n_points) {
-            const float x = px[i], y = py[i], z = pz[i];
-            // crop_pc in the cloud's frame: float32 point against float64 bounds, strict on both sides
-            keep = (double)x > j.lo1[0] && (double)x < j.hi1[0] && (double)y > j.lo1[1] && (double)y < j.hi1[1] &&
-                   (double)z > j.lo1[2] && (double)z < j.hi1[2];
-            if (keep && j.label_out) {
-                // get_label_by_box on the first crop: the same translate / rotate / strict test in the ground-truth box's frame
-                const double tx = (double)(float)((double)x + j.ltrans[0]);
-                const double ty = (double)(float)((double)y + j.ltrans[1]);
-                const double tz = (double)(float)((double)z + j.ltrans[2]);
-                const float lx = (float)fma(j.lrot[2], tz, fma(j.lrot[1], ty, j.lrot[0] * tx));
-                const float ly = (float)fma(j.lrot[5], tz, fma(j.lrot[4], ty, j.lrot[3] * tx));
-                const float lz = (float)fma(j.lrot[8], tz, fma(j.lrot[7], ty, j.lrot[6] * tx));
-                label = (double)lx > j.llo[0] && (double)lx < j.lhi[0] && (double)ly > j.llo[1] && (double)ly < j.lhi[1] &&
-                        (double)lz > j.llo[2] && (double)lz < j.lhi[2];
-            }
-            if (keep) {
-                // PointCloud.translate: points[i,:] = points[i,:] + x[i] (float64 sum stored to the float32 array)
-                const double tx = (double)(float)((double)x + j.trans[0]);
-                const double ty = (double)(float)((double)y + j.trans[1]);
-                const double tz = (double)(float)((double)z + j.trans[2]);
-                // PointCloud.rotate: np.dot(rot (f64), points) stored to float32
-                ox = (float)fma(j.rot[2], tz, fma(j.rot[1], ty, j.rot[0] * tx));
-                oy = (float)fma(j.rot[5], tz, fma(j.rot[4], ty, j.rot[3] * tx));
-                oz = (float)fma(j.rot[8], tz, fma(j.rot[7], ty, j.rot[6] * tx));
-                keep = (double)ox > j.lo2[0] && (double)ox < j.hi2[0] && (double)oy > j.lo2[1] && (double)oy < j.hi2[1] &&
-                       (double)oz > j.lo2[2] && (double)oz < j.hi2[2];
-            }
-        }
+        if (i < j.n_points) keep = crop_point(j, px[i], py[i], pz[i], j.label_out != nullptr, ox, oy, oz, label);
         int total;
         const int r = written + block_rank<T>(keep, wsum, total);
         if (keep && r < j.capacity) {
@@ -133,6 +139,70 @@ template <int T>
 __global__ __launch_bounds__(T) void crop_compact_kernel(const ptt_crop_job* __restrict__ jobs) {
     const ptt_crop_job j = jobs[blockIdx.x];
     crop_compact_body<T>(j);
+}
+
+// ---- ptt_crop_scan_f32: the same crops with every job spread over (chunks of the cloud) workgroups ----
+// A full LiDAR scan is 35k-130k points; one workgroup per job (above) walks it in ~n / 1024 dependent load -> ballot -> barrier
+// rounds on one CU. Here workgroup (c, job) owns points [c * C, (c + 1) * C) of the job's cloud, C = PTT_SCAN_CROP_CHUNK = one
+// point per thread. Two launches, no workgroup ever waits for another and no atomic is used:
+//   count  counts[job][c] = survivors of chunk c (0 for chunks past the job's n_points);
+//   write  first row of chunk c = sum of counts[job][0 .. c) (at most a few hundred values, summed in integers: any order
+//          gives the same number), the test is repeated and survivor r of the chunk goes to that row + its rank inside the chunk.
+//          A chunk without survivors returns at once; the LAST chunk of the grid also writes *count.
+// The order of the rows is the order of the points, as in crop_compact_body, and the values come from the same crop_point.
+constexpr int kScanChunk = PTT_SCAN_CROP_CHUNK;
+
+__global__ __launch_bounds__(kScanChunk) void crop_scan_count_kernel(const ptt_crop_job* __restrict__ jobs, int32_t* __restrict__ counts) {
+    __shared__ int wsum[kScanChunk / 64];
+    const ptt_crop_job& j = jobs[blockIdx.y];
+    const int n = j.n_points;
+    const int base = (int)blockIdx.x * kScanChunk;                      // < max_points + C <= 2^31 - 1 (checked by the host)
+    int32_t* slot = counts + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (base >= n) {                                                    // uniform: a chunk past this job's cloud
+        if (threadIdx.x == 0) *slot = 0;
+        return;
+    }
+    const int i = base + (int)threadIdx.x;
+    bool keep = false, label = false;
+    float ox, oy, oz;
+    if (i < n) keep = crop_point(j, j.points[i], j.points[j.ld + i], j.points[2 * j.ld + i], false, ox, oy, oz, label);
+    int total;
+    block_rank<kScanChunk>(keep, wsum, total);
+    if (threadIdx.x == 0) *slot = total;
+}
+
+__global__ __launch_bounds__(kScanChunk) void crop_scan_write_kernel(const ptt_crop_job* __restrict__ jobs, const int32_t* __restrict__ counts) {
+    __shared__ int wsum[kScanChunk / 64];
+    const int32_t* c = counts + (size_t)blockIdx.y * gridDim.x;
+    const int own = c[blockIdx.x];
+    const bool last = blockIdx.x == gridDim.x - 1;
+    if (own == 0 && !last) return;                                      // uniform: nothing to place, and not the one that reports
+    // rows in front of this chunk: every thread adds a strided share of the earlier chunks' counts, then one sum per workgroup
+    int part = 0;
+    for (int k = threadIdx.x; k < (int)blockIdx.x; k += kScanChunk) part += c[k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
+    __syncthreads();
+    int first = 0;
+#pragma unroll
+    for (int w = 0; w < kScanChunk / 64; ++w) first += wsum[w];
+    __syncthreads();                                                    // block_rank reuses wsum
+    const ptt_crop_job& j = jobs[blockIdx.y];
+    if (own != 0) {
+        const int i = (int)blockIdx.x * kScanChunk + (int)threadIdx.x;
+        bool keep = false, label = false;
+        float ox = 0.f, oy = 0.f, oz = 0.f;
+        if (i < j.n_points) keep = crop_point(j, j.points[i], j.points[j.ld + i], j.points[2 * j.ld + i], false, ox, oy, oz, label);
+        int total;
+        const int r = first + block_rank<kScanChunk>(keep, wsum, total);
+        if (keep && r < j.capacity) {
+            j.out[(size_t)r * 3 + 0] = ox;
+            j.out[(size_t)r * 3 + 1] = oy;
+            j.out[(size_t)r * 3 + 2] = oz;
+        }
+    }
+    if (last && threadIdx.x == 0) *j.count = first + own;               // may exceed capacity, as crop_compact_body's
 }
 
 __device__ __forceinline__ void seg_point(const ptt_regularize_job& j, const int* cnt, int idx, float* dst) {
@@ -536,6 +606,27 @@ extern "C" int ptt_crop_compact_f32(const ptt_crop_job* jobs_device, int n_jobs,
     if (!jobs_device) return fail(PTT_EINVAL, "ptt_crop_compact_f32: null job array");
     hipLaunchKernelGGL((crop_compact_kernel<1024>), dim3(n_jobs), dim3(1024), 0, as_stream(stream), jobs_device);
     return check_launch("crop_compact_kernel");
+}
+
+static int scan_chunks(int max_points) { return max_points > 0 ? (max_points - 1) / kScanChunk + 1 : 1; }
+
+extern "C" size_t ptt_crop_scan_workspace(int n_jobs, int max_points) {
+    if (n_jobs <= 0 || max_points < 0) return 0;
+    return (size_t)n_jobs * (size_t)scan_chunks(max_points) * sizeof(int32_t);
+}
+
+extern "C" int ptt_crop_scan_f32(const ptt_crop_job* jobs_device, int n_jobs, int max_points, void* ws, size_t ws_bytes, ptt_stream_t stream) {
+    if (n_jobs < 0 || n_jobs > 65535 || max_points < 0 || max_points > 0x7fffffff - kScanChunk)
+        return fail(PTT_EINVAL, "ptt_crop_scan_f32: n_jobs=%d (0..65535) max_points=%d", n_jobs, max_points);
+    if (n_jobs == 0) return PTT_OK;
+    if (!jobs_device || !ws) return fail(PTT_EINVAL, "ptt_crop_scan_f32: null job array or workspace");
+    const size_t need = ptt_crop_scan_workspace(n_jobs, max_points);
+    if (ws_bytes < need) return fail(PTT_EINVAL, "ptt_crop_scan_f32: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    const dim3 grid(scan_chunks(max_points), n_jobs);
+    int32_t* counts = static_cast<int32_t*>(ws);
+    hipLaunchKernelGGL(crop_scan_count_kernel, grid, dim3(kScanChunk), 0, as_stream(stream), jobs_device, counts);
+    hipLaunchKernelGGL(crop_scan_write_kernel, grid, dim3(kScanChunk), 0, as_stream(stream), jobs_device, (const int32_t*)counts);
+    return check_launch("crop_scan_kernel");
 }
 
 extern "C" int ptt_crop_regularize_f32(const ptt_crop_job* crop_jobs, const ptt_regularize_job* reg_jobs_device, int n_jobs,

@@ -788,6 +788,49 @@ def crop_compact_pinned(jobs_pinned, n_jobs, device):
     _launch("ptt_crop_compact_f32", device, ctypes.c_void_p(jobs_pinned.data_ptr()), int(n_jobs), timed='ptt_crop_compact_f32')
 
 
+SCAN_CROP_CHUNK = _lib.DEFINES["PTT_SCAN_CROP_CHUNK"]      # points per workgroup of ptt_crop_scan_f32
+
+
+def crop_scan_check(jobs_np, n_jobs, max_points):
+    """What ptt_crop_scan_f32 cannot report from the device, checked on the HOST table: ValueError for a job with labels
+    (label_out), an append job, or a cloud longer than max_points (its tail would be ignored)."""
+    jobs = jobs_np[:int(n_jobs)]
+    if len(jobs) != int(n_jobs) or int(max_points) < 0:
+        raise ValueError("crop_scan: the table holds %d jobs, n_jobs=%d, max_points=%d" % (len(jobs_np), n_jobs, max_points))
+    if np.any(jobs['label_out'] != 0):
+        raise ValueError("crop_scan: label_out is not supported (training crops take ptt_crop_compact_f32)")
+    if np.any(jobs['append'] != 0):
+        raise ValueError("crop_scan: append jobs are not supported (SHAPE_AGGREGATION = all takes ptt_crop_compact_f32)")
+    if len(jobs) and (int(jobs['n_points'].max()) > int(max_points) or int(jobs['n_points'].min()) < 0):
+        raise ValueError("crop_scan: n_points must lie in 0..max_points=%d, got %d..%d" % (max_points, jobs['n_points'].min(), jobs['n_points'].max()))
+
+
+def crop_scan_workspace(n_jobs, max_points):
+    """ptt_crop_scan_workspace: bytes of workspace ptt_crop_scan_f32 needs for this launch."""
+    return int(_host("ptt_crop_scan_workspace", int(n_jobs), int(max_points)))
+
+
+def crop_scan_device(jobs_dev, n_jobs, max_points, ws=None):
+    """ptt_crop_scan_f32 over a table that is already on the device and was checked on the host (crop_scan_check). ws: a device
+    buffer of at least crop_scan_workspace(n_jobs, max_points) bytes (default: a fresh one)."""
+    if ws is None:
+        ws = _ws(crop_scan_workspace(n_jobs, max_points), jobs_dev.device)
+    _launch("ptt_crop_scan_f32", jobs_dev.device, _ptr(jobs_dev), int(n_jobs), int(max_points), _ptr(ws), ws.numel() * ws.element_size(),
+            timed='ptt_crop_scan_f32')
+
+
+def crop_scan(jobs_np, n_jobs, max_points, device, out=None):
+    """ptt_crop_scan_f32: the crops of crop_compact, every job spread over chunks of SCAN_CROP_CHUNK points of its cloud — for
+    whole LiDAR scans. jobs_np: the HOST table (CROP_JOB array); it is checked (crop_scan_check: ValueError for label_out, append,
+    n_points > max_points), uploaded (into `out`, a device uint8 buffer of the table's size, if given) and launched.
+    max_points: an upper bound on every job's n_points. -> the device table."""
+    crop_scan_check(jobs_np, n_jobs, max_points)
+    with torch.cuda.device(device):
+        jobs_dev = upload_jobs(jobs_np, out)
+    crop_scan_device(jobs_dev, n_jobs, max_points)
+    return jobs_dev
+
+
 def crop_regularize_pinned(crop_jobs_pinned, reg_jobs_dev, n_jobs, draws):
     """ptt_crop_regularize_f32: crop job w then resampling job w per workgroup, the crop table read from pinned host memory."""
     _launch("ptt_crop_regularize_f32", reg_jobs_dev.device, ctypes.c_void_p(crop_jobs_pinned.data_ptr()), _ptr(reg_jobs_dev), int(n_jobs),

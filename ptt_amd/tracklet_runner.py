@@ -79,11 +79,12 @@ class _BoxedForward(object):
 class TrackletRunner(object):
     def __init__(self, tracker, device, batch=1, search_size=1024, template_size=512, search_offset=0.0,
                  search_scale=1.25, model_offset=0.0, model_scale=1.25, use_z=True, use_graph=True,
-                 shape_aggregation="firstandprevious", ref_box="previous_result"):
+                 shape_aggregation="firstandprevious", ref_box="previous_result", uploaded=False):
         """`tracker`: ptt_amd.models.trackers.PTT in eval mode on `device`. Sizes / offsets / scales are
         DATA_CONFIG.{SEARCH,TEMPLATE}_INPUT_SIZE, SEARCH_BB_*, MODEL_BB_* and USE_Z_AXIS
         (tools/cfgs/kitti_models/ptt.yaml:8-17); shape_aggregation / ref_box are TEST.SHAPE_AGGREGATION / TEST.REF_BOX
-        (:149-150), parsed by tracking_modes."""
+        (:149-150), parsed by tracking_modes. uploaded=True takes the uploaded-table branch (job table in device memory,
+        model graph with the selection on the device) at a handful of tracklets too: what OnlineTracker drives."""
         self.shape, self.ref_box = tracking_modes(shape_aggregation, ref_box)
         self.tracker = tracker
         self.device = torch.device(device)
@@ -106,7 +107,7 @@ class TrackletRunner(object):
         self.draws = ops.mt19937_draws(dev, max(8192, 4 * max(self.S, self.T) + 1024))
         # a handful of tracklets: the crop table rides in the crop launch's arguments (no upload), and the host picks the best
         # proposal itself from the (B,P,5) read-back — two launches less per frame of a chain that is launches
-        self.few = 2 * B <= ops.CROP_JOBS_BY_VALUE_MAX
+        self.few = 2 * B <= ops.CROP_JOBS_BY_VALUE_MAX and not uploaded
         if self.few and use_graph:
             # one read-back buffer: (B,P,5) proposals, then the (B,2,2) resampling counts
             self.P = int(tracker.box_voting_head.model_cfg.SA_CONFIG.NPOINTS)
@@ -158,11 +159,7 @@ class TrackletRunner(object):
                 self.ptr[i, b], self.ld[i, b], self.npts[i, b] = t.data_ptr(), t.stride(0), t.shape[1]
                 cap = max(cap, t.shape[1])
             self.clouds.append(row)
-        self.cap = cap
-        self.crop_out = torch.zeros((B, 3, cap, 3), dtype=torch.float32, device=dev)   # slot 0 search, 1 first, 2 previous
-        esz = self.crop_out.element_size()
-        self.out_ptr = (self.crop_out.data_ptr() + (np.arange(B)[:, None] * 3 + np.arange(3)[None]) * (cap * 3 * esz)).astype(np.uint64)
-        self.cnt_ptr = (self.counts.data_ptr() + (np.arange(B)[:, None] * 3 + np.arange(3)[None]) * 4).astype(np.uint64)
+        self._crop_slots(cap)
         self.ptr[self.npts == 0] = self.crop_out.data_ptr()        # empty jobs still carry a valid address
         # per tracked frame i the cloud fields of the interleaved 2B-job table: even jobs = frame i, odd jobs = frame i - 1
         ff = [np.zeros((T, 2 * B), dt) for dt in (np.uint64, np.int64, np.int32)]
@@ -176,7 +173,32 @@ class TrackletRunner(object):
             lengths = np.array([len(c) for c, _ in tracklets] + [0] * (B - len(tracklets)))
             ff[2][:, 1::2] *= (np.arange(T)[:, None] < lengths[None, :])
         self.frame_fields = ff
-        # the resampling jobs never change within a group: fixed segment / output pointers
+        rj = self._resample_table()
+        if self.shape == "all":
+            # every group starts with an empty store; a store that grew in an earlier group keeps its capacity
+            if self.store is None or self.store.shape[1] < cap:
+                self.store = torch.zeros((B, cap, 3), dtype=torch.float32, device=dev)
+                self.store_count = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.store_count.zero_()
+            self.store_total = np.zeros(B, np.int64)
+            self._store_tables()                                   # uploads the resampling table
+        else:
+            ops.upload_jobs(rj, self.reg_jobs_dev)
+
+    def _crop_slots(self, cap):
+        """The crop outputs of every tracklet, (B, 3, cap, 3): slot 0 search, 1 first-frame, 2 previous-frame template segment,
+        with the job tables' pointers to the slots (out_ptr) and to their device counts (cnt_ptr), both (B, 3)."""
+        B = self.B
+        self.cap = cap
+        self.crop_out = torch.zeros((B, 3, cap, 3), dtype=torch.float32, device=self.device)
+        esz = self.crop_out.element_size()
+        self.out_ptr = (self.crop_out.data_ptr() + (np.arange(B)[:, None] * 3 + np.arange(3)[None]) * (cap * 3 * esz)).astype(np.uint64)
+        self.cnt_ptr = (self.counts.data_ptr() + (np.arange(B)[:, None] * 3 + np.arange(3)[None]) * 4).astype(np.uint64)
+
+    def _resample_table(self):
+        """The 2B resampling jobs (job 2b: tracklet b's search cloud, 2b + 1: its template) over the current crop slots and model
+        input buffers -> self.reg_jobs. They never change within a group: fixed segment / output pointers."""
+        B, cap = self.B, self.cap
         rj = np.zeros(2 * B, ops.REGULARIZE_JOB)
         s, t = rj[0::2], rj[1::2]
         s['seg'][:, 0], s['seg_count'][:, 0], s['seg_capacity'][:, 0] = self.out_ptr[:, 0], self.cnt_ptr[:, 0], cap
@@ -192,16 +214,7 @@ class TrackletRunner(object):
         t['out'] = self.template.data_ptr() + np.arange(B) * (self.T * 3 * 4)
         t['info'] = self.info.data_ptr() + np.arange(B) * 16 + 8
         self.reg_jobs = rj
-        if self.shape == "all":
-            # every group starts with an empty store; a store that grew in an earlier group keeps its capacity
-            if self.store is None or self.store.shape[1] < cap:
-                self.store = torch.zeros((B, cap, 3), dtype=torch.float32, device=dev)
-                self.store_count = torch.zeros(B, dtype=torch.int32, device=dev)
-            self.store_count.zero_()
-            self.store_total = np.zeros(B, np.int64)
-            self._store_tables()                                   # uploads the resampling table
-        else:
-            ops.upload_jobs(rj, self.reg_jobs_dev)
+        return rj
 
     def _store_tables(self):
         """SHAPE_AGGREGATION = all: point the template crop jobs (odd entries of the pinned crop table: append into the store) and
@@ -354,12 +367,7 @@ class TrackletRunner(object):
             else:
                 self._frame_jobs(i, extra_search[i], ref)
                 self._launch_jobs()
-                ops.regularize(self.reg_jobs_dev, 2 * B, self.draws)
-                self.info_host.copy_(self.info, non_blocking=True)   # behind the resampling, ahead of the model: off the frame's tail
-                rows = self._forward()
-                if self.result_host is None or self.result_host.shape != rows.shape:
-                    self.result_host = torch.empty(tuple(rows.shape), dtype=torch.float32).pin_memory()
-                self.result_host.copy_(rows, non_blocking=True)
+                self._enqueue_model()
             self._done.record(torch.cuda.current_stream(self.device))
             if prof is not None:
                 ev1.record(torch.cuda.current_stream(self.device))
@@ -411,6 +419,15 @@ class TrackletRunner(object):
                 next(gen)
             except StopIteration as stop:
                 return stop.value
+
+    def _enqueue_model(self):
+        """Behind a frame's crop launch: resampling into the model's input buffers, the model, and the two read-backs."""
+        ops.regularize(self.reg_jobs_dev, 2 * self.B, self.draws)
+        self.info_host.copy_(self.info, non_blocking=True)       # behind the resampling, ahead of the model: off the frame's tail
+        rows = self._forward()
+        if self.result_host is None or self.result_host.shape != rows.shape:
+            self.result_host = torch.empty(tuple(rows.shape), dtype=torch.float32).pin_memory()
+        self.result_host.copy_(rows, non_blocking=True)
 
     def _frame_body(self):
         ops.crop_regularize_pinned(self.crop_jobs_host, self.reg_jobs_dev, 2 * self.B, self.draws)     # crop w, then resampling w

@@ -1,0 +1,230 @@
+"""OnlineTracker on the GPU: several targets that come and go on one live scan per step, against TrackletRunner — the oracle —
+bit for bit. For every target and step, centre, wlh, quaternion and score equal what TrackletRunner(tracker, dev, batch=S) gives
+for that target ALONE on the scans since its `add`, with the box it was added with as frame 0 (the same S on both sides: the
+forward's kernel choice depends on the batch width, a frame's result does not depend on its batch-mates).
+
+The scene: three synthetic tracklets of 7 frames 40 m apart, concatenated per frame into one scan of 5k - 14k points.
+Life cycle at S = 6: A added at step 0, B at 2, C at 3; A dropped at 5; B dropped and added again at step 6. At S = 2 the third
+target cannot be held at step 3: there the add of C is REFUSED (ValueError, state unchanged — asserted), and C is added at step 5
+in the call that drops A; everything else is the same."""
+import numpy as np
+import pytest
+import torch
+
+from ptt_amd import synth
+
+pytestmark = pytest.mark.gpu
+T = 7
+CAPACITY = 16384
+TRACKLET_OF = {"A": 0, "B": 1, "C": 2}
+_cache = {}
+
+
+def _scene():
+    if "scene" not in _cache:
+        shifts = np.array([(0, 0, 0), (40, 0, 0), (0, 40, 0)], np.float32)
+        tr = [synth.tracklet(300 + k, T) for k in range(3)]
+        scans = [np.ascontiguousarray(np.concatenate([tr[k][0][t] + shifts[k][:, None] for k in range(3)], axis=1)) for t in range(T)]
+        assert all(s.dtype == np.float32 and 5000 < s.shape[1] <= CAPACITY for s in scans)
+        boxes = [[((b[0].astype(np.float32) + shifts[k]).astype(np.float64), b[1], b[2]) for b in tr[k][1]] for k in range(3)]
+        _cache["scene"] = (scans, boxes)
+    return _cache["scene"]
+
+
+def _make_tracker(dev, seed=2):
+    from ptt_amd.config import StubDataset, ptt_model_cfg
+    from ptt_amd.hot_path import randomize_
+    from ptt_amd.models import build_network
+    tracker = randomize_(build_network(ptt_model_cfg(), 1, StubDataset()), seed=seed).to(dev).eval()
+    with torch.no_grad():                                  # small regression outputs, as a trained model's are
+        tracker.box_voting_head.refine_layer[-1].conv.weight.mul_(0.05)
+        tracker.box_voting_head.refine_layer[-1].conv.bias.mul_(0.05)
+    return tracker
+
+
+def _tracker(dev):
+    if "tracker" not in _cache:
+        _cache["tracker"] = _make_tracker(dev)
+    return _cache["tracker"]
+
+
+def _plan(S):
+    """-> per step (adds, drops, refused adds)."""
+    adds, drops, refused = {0: ["A"], 2: ["B"], 6: ["B"]}, {5: ["A"], 6: ["B"]}, {}
+    if S >= 3:
+        adds[3] = ["C"]
+    else:
+        refused[3] = ["C"]
+        adds[5] = ["C"]
+    return [(adds.get(t, []), drops.get(t, []), refused.get(t, [])) for t in range(T)]
+
+
+def _lives(S):
+    """[(id, t_add, t_end)] of the plan: a target's life ends with its drop or with the last scan."""
+    live, lives = {}, []
+    for t, (adds, drops, _) in enumerate(_plan(S)):
+        for i in drops:
+            lives.append((i, live.pop(i), t))
+        for i in adds:
+            live[i] = t
+    return lives + [(i, t0, T) for i, t0 in live.items()]
+
+
+def _expected(dev, S, shape):
+    """{(id, t_add): the runner's result rows} — computed once per (S, shape) and shared, never modified."""
+    key = ("expected", S, shape)
+    if key not in _cache:
+        from ptt_amd.tracklet_runner import TrackletRunner
+        scans, boxes = _scene()
+        runner = TrackletRunner(_tracker(dev), dev, batch=S, shape_aggregation=shape)
+        out = {}
+        for i, t0, t1 in _lives(S):
+            out[(i, t0)] = runner.run([(scans[t0:t1], [boxes[TRACKLET_OF[i]][t0]] * (t1 - t0))])[0]
+            assert len(out[(i, t0)]) == t1 - t0
+        _cache[key] = out
+    return _cache[key]
+
+
+def _same(got, want, what):
+    np.testing.assert_array_equal(got[0], want[0], err_msg="%s centre" % (what,))
+    np.testing.assert_array_equal(got[1], want[1], err_msg="%s wlh" % (what,))
+    np.testing.assert_array_equal(got[2], want[2], err_msg="%s quaternion" % (what,))
+    if len(want) == 3:
+        assert got[3] is None, what
+    else:
+        assert got[3] == want[3], (what, got[3], want[3])
+
+
+def _bad_calls(ot, scan, t):
+    """Every refusal, each followed by a look at the state: the ids and the boxes are what they were."""
+    scans, boxes = _scene()
+    ids = list(ot.targets)
+    state = (ot.boxes.copy(), ot.rng_pos.copy(), ot.cur, ot.n_prev)
+    box = boxes[2][t]
+    calls = [dict(scan=scan.astype(np.float64)), dict(scan=np.ascontiguousarray(scan.T)), dict(scan=scan[:, ::2]), dict(scan=scan[0]),
+             dict(scan=list(scan)), dict(scan=torch.from_numpy(scan).double()), dict(scan=np.zeros((3, CAPACITY + 1), np.float32)),
+             dict(scan=scan, drop=("nobody",)), dict(scan=scan, add={"X": (box[0], box[1])}),
+             dict(scan=scan, add={k: box for k in "UVWXYZ0"})]
+    if ids:
+        calls.append(dict(scan=scan, add={ids[0]: box}))
+    for kw in calls:
+        with pytest.raises(ValueError):
+            ot.step(**kw)
+        assert ot.targets == ids and ot.cur == state[2] and ot.n_prev == state[3]
+        assert np.array_equal(ot.boxes, state[0]) and np.array_equal(ot.rng_pos, state[1])
+    return len(calls)
+
+
+def _run_life_cycle(dev, S, shape, scan_crop, scan_kind="numpy", bad_calls=False, use_graph=True):
+    from ptt_amd.online_tracker import OnlineTracker
+    scans, boxes = _scene()
+    want = _expected(dev, S, shape)
+    ot = OnlineTracker(_tracker(dev), dev, slots=S, scan_capacity=CAPACITY, shape_aggregation=shape, scan_crop=scan_crop, use_graph=use_graph)
+    born, n_moved, n_checked = {}, 0, 0
+    for t, (adds, drops, refused) in enumerate(_plan(S)):
+        scan = scans[t]
+        if scan_kind == "device":
+            scan = torch.from_numpy(scan).to(dev)
+        elif scan_kind == "pinned":
+            scan = torch.from_numpy(scan).pin_memory()
+        if refused:
+            before = list(ot.targets)
+            with pytest.raises(ValueError, match="slots"):
+                ot.step(scan, add={i: boxes[TRACKLET_OF[i]][t] for i in refused})
+            assert ot.targets == before
+        if bad_calls:
+            assert _bad_calls(ot, scans[t], t) >= 10
+        for i in drops:
+            del born[i]
+        for i in adds:
+            born[i] = t
+        got = ot.step(scan, add={i: boxes[TRACKLET_OF[i]][t] for i in adds}, drop=drops)
+        assert list(got) == list(ot.targets) and sorted(got) == sorted(born)
+        for i in adds:                                       # a new target starts where the runner's frame 0 does, in a reused slot too
+            assert ot.rng_pos[ot.table.slot_of[i]] == 0
+        for i, t0 in born.items():
+            row = want[(i, t0)][t - t0]
+            _same(got[i], row, "target %s step %d (frame %d)" % (i, t, t - t0))
+            n_checked += 1
+            n_moved += int(t > t0 and float(np.abs(got[i][0] - want[(i, t0)][0][0]).max()) > 1e-6)
+    assert n_checked == sum(t1 - t0 for _, t0, t1 in _lives(S)) and n_moved > 0
+    return ot
+
+
+@pytest.mark.parametrize("scan_crop", [True, False])
+@pytest.mark.parametrize("shape", ["first", "previous", "firstandprevious"])
+@pytest.mark.parametrize("S", [2, 6])
+def test_life_cycle_equals_the_runner(dev, S, shape, scan_crop):
+    _run_life_cycle(dev, S, shape, scan_crop)
+
+
+@pytest.mark.parametrize("scan_kind", ["device", "pinned"])
+def test_tensor_scans_give_what_numpy_scans_give(dev, scan_kind):
+    """A device tensor and a pinned host tensor: the same boxes as the numpy scans of the test above (the same expectation)."""
+    _run_life_cycle(dev, 6, "firstandprevious", None, scan_kind=scan_kind)
+
+
+def test_eager_model_gives_what_the_graph_gives(dev):
+    """use_graph=False launches the same kernels without a capture: the same boxes."""
+    _run_life_cycle(dev, 6, "firstandprevious", None, use_graph=False)
+
+
+def test_refused_calls_leave_the_state_unchanged(dev):
+    """Before every step: a wrong dtype, wrong shapes, a non-contiguous array, a list, N over the capacity, an unknown drop, a
+    malformed box, more adds than slots, an id that is already live — each a ValueError, after which the step still matches the
+    runner. S = 2 also refuses the third target (module docstring)."""
+    _run_life_cycle(dev, 2, "firstandprevious", True, bad_calls=True)
+
+
+def test_empty_scan_gives_what_the_runner_gives_for_an_empty_cloud(dev):
+    from ptt_amd.online_tracker import OnlineTracker
+    from ptt_amd.tracklet_runner import TrackletRunner
+    scans, boxes = _scene()
+    clouds = [scans[0], scans[1], np.zeros((3, 0), np.float32), scans[3], scans[4]]
+    want = TrackletRunner(_tracker(dev), dev, batch=2).run([(clouds, [boxes[0][0]] * len(clouds))])[0]
+    for scan_crop in (True, False):
+        ot = OnlineTracker(_tracker(dev), dev, slots=2, scan_capacity=CAPACITY, scan_crop=scan_crop)
+        for t, cloud in enumerate(clouds):
+            got = ot.step(cloud, add={"A": boxes[0][0]} if t == 0 else None)
+            _same(got["A"], want[t], "step %d" % t)
+
+
+def test_all_is_refused_on_the_device_too(dev):
+    from ptt_amd.online_tracker import OnlineTracker
+    with pytest.raises(ValueError, match="out of scope"):
+        OnlineTracker(_tracker(dev), dev, slots=2, shape_aggregation="all")
+
+
+def test_reset_forgets_the_targets(dev):
+    ot = _run_life_cycle(dev, 6, "previous", None)
+    assert ot.targets
+    ot.reset()
+    assert ot.targets == []
+    scans, boxes = _scene()
+    want = _expected(dev, 6, "previous")[("A", 0)]
+    for t in range(3):                                       # the same tracker object again, from the start
+        _same(ot.step(scans[t], add={"A": boxes[0][0]} if t == 0 else None)["A"], want[t], "after reset, step %d" % t)
+
+
+def test_load_state_dict_between_steps_recaptures(dev):
+    """New weights between two steps: the next step is computed with them. SHAPE_AGGREGATION = previous, where a target's state is
+    its box and the previous scan alone: a FRESH tracker object with the new weights, given the box after step 1 as a new target
+    on scan 1, must produce the same step 2."""
+    from ptt_amd.online_tracker import OnlineTracker
+    scans, boxes = _scene()
+    tracker = _make_tracker(dev, seed=2)                     # its own object: its weights are overwritten below
+    new = _make_tracker(dev, seed=3)
+    ot = OnlineTracker(tracker, dev, slots=2, scan_capacity=CAPACITY, shape_aggregation="previous")
+    ot.step(scans[0], add={"A": boxes[0][0]})
+    after1 = ot.step(scans[1])["A"]
+    graph = ot.core._graph
+    tracker.load_state_dict(new.state_dict())
+    got = ot.step(scans[2])["A"]
+    assert ot.core._graph is not graph and ot.core._graph.captures == 1          # a new capture, not a replay of the old weights
+    fresh = OnlineTracker(new, dev, slots=2, scan_capacity=CAPACITY, shape_aggregation="previous")
+    fresh.step(scans[1], add={"A": after1[:3]})
+    _same(got, fresh.step(scans[2])["A"], "step 2 with the new weights")
+    # ... and it is not what the old weights give
+    old = OnlineTracker(_tracker(dev), dev, slots=2, scan_capacity=CAPACITY, shape_aggregation="previous")
+    old.step(scans[1], add={"A": after1[:3]})
+    assert not np.array_equal(old.step(scans[2])["A"][0], got[0])
