@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 30
+#define PTT_ABI_VERSION 31
 
 enum {
     PTT_OK = 0,
@@ -418,8 +418,10 @@ int ptt_cosine_map_f32(const float* search_feat, int64_t s_sb, int64_t s_sn, int
  *   attn = softmax_j(a / sqrt(D));    res_i = sum_j attn * (v_j + delta)
  * replaces TransformerBlock.forward lines                  variants.py:158-163
  *   qkv (B,N,3*D) = [q | k | v] rows (from ptt_linear_f32 with the stacked weight),
- *   knn (B,N,k) i32. D = 512 and k = 16 are the instantiated configuration; N must be even (a tile holds two points of
- *   one cloud; PTT_EUNSUPPORTED otherwise).
+ *   knn (B,N,k) i32. One head (heads 0 or 1): D 128, 256 or 512 and k 8, 16 or 32 are instantiated; several heads: D = 512
+ *   and k = 16 only (PTT_EUNSUPPORTED otherwise). A 32-row tile holds 32 / k whole points of one cloud, so N % (32 / k) == 0:
+ *   at k = 8, N must be a multiple of 4; at k = 16, N must be even (a tile holds two points of
+ *   one cloud; PTT_EUNSUPPORTED otherwise); at k = 32 any N. N >= k. A refused launch (PTT_EUNSUPPORTED) writes nothing.
  *   res (B,N,D); attn (B,N,k,D) or NULL (the heads discard it: centroids_voting_head.py:76).
  * ------------------------------------------------------------------------------- */
 typedef struct ptt_attn_desc {

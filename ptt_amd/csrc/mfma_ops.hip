@@ -2017,8 +2017,9 @@ __global__ __launch_bounds__(256, 2) void sa_wave_kernel(SaParams p) {   // 2 wa
 }
 
 // ------------------------------------------------------------------------------------------
-// Point-Transformer pair kernel. A workgroup owns 2 points x 16 neighbours = 32 pair rows
-// and all D = 512 channels; wave w owns column tiles w, w+4, w+8, w+12.
+// Point-Transformer pair kernel. A workgroup owns 32 / KNN points x KNN neighbours = 32 pair rows
+// (4 x 8, 2 x 16 or 1 x 32) and all D channels (128, 256 or 512); wave w owns column tiles
+// w, w+4, .. of the D / 32 (one, two or four of them).
 // ------------------------------------------------------------------------------------------
 struct AttnParams {
     const float* xyz; const float* rel; const int32_t* knn; const float* qkv; const float* Wd1p;
@@ -2085,7 +2086,7 @@ __device__ __forceinline__ void prefetch_first_block_heads(const float* Wp, int 
     for (int i = 0; i < NB; ++i) pre[i] = bp[(size_t)((w + 4 * i) % TPH) * 64];
 }
 
-template <int D>
+template <int D, int KNN>
 __global__ __launch_bounds__(256, 2) void pt_attn_pair_kernel(AttnParams p) {
     constexpr int HEADS = 1;
 #include "pt_attn_pair_body.h"
@@ -2093,7 +2094,7 @@ __global__ __launch_bounds__(256, 2) void pt_attn_pair_kernel(AttnParams p) {
 
 template <int HEADS>
 __global__ __launch_bounds__(256, 2) void pt_attn_pair_heads_kernel(AttnParams p) {
-    constexpr int D = 512;
+    constexpr int D = 512, KNN = 16;
 #include "pt_attn_pair_body.h"
 }
 
@@ -2606,11 +2607,20 @@ extern "C" int ptt_cosine_map_f32(const float* search_feat, int64_t s_sb, int64_
     return check_launch("cos_map_kernel");
 }
 
+// D x KNN instantiations of the single-head pair kernel
+#define PTT_PAIR_SHAPES(X) X(128, 8) X(128, 16) X(128, 32) X(256, 8) X(256, 16) X(256, 32) X(512, 8) X(512, 16) X(512, 32)
+
 extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream) {
     if (!d) return fail(PTT_EINVAL, "ptt_pt_attn_pair_f32: null descriptor");
     if (d->B < 0 || d->N <= 0) return fail(PTT_EINVAL, "ptt_pt_attn_pair_f32: B=%d N=%d", d->B, d->N);
-    if (d->D != 512 || d->k != 16)
-        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: D=%d k=%d (D=512, k=16 is instantiated)", d->D, d->k);
+    const int heads = d->heads ? d->heads : 1;
+    if ((d->D != 128 && d->D != 256 && d->D != 512) || (d->k != 8 && d->k != 16 && d->k != 32))
+        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: D=%d k=%d (D 128, 256, 512 x k 8, 16, 32 are instantiated)", d->D, d->k);
+    if (heads != 1 && heads != 2 && heads != 4 && heads != 8)
+        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d (1, 2, 4, 8 are instantiated)", d->heads);
+    if (heads > 1 && (d->D != 512 || d->k != 16))
+        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d D=%d k=%d (several heads: D=512, k=16 is instantiated)", heads,
+                    d->D, d->k);
     if (d->B == 0) return PTT_OK;
     if (!d->xyz || !d->knn || !d->qkv || !d->Wd1p || !d->Wd2p || !d->bd2 || !d->Wg1p || !d->bg1 ||
         !d->Wg2p || !d->res)
@@ -2622,28 +2632,34 @@ extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream)
     p.BN = d->B * d->N; p.N = d->N;
     p.first_wave = 512; p.stagger = dev_switches().pair_stagger;
     p.dbg = dev_switches().stamps;
-    if ((d->N & 1) != 0)
-        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: N=%d must be even (a tile holds two points of one cloud)",
-                    d->N);
-    const int heads = d->heads ? d->heads : 1;
-    int lds = (32 * (512 + 4) + 32 + 32 * 12) * (int)sizeof(float);
+    const int pts = 32 / d->k;                                        // points per 32-row tile
+    if (d->N % pts != 0) {
+        if (d->k == 16)
+            return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: N=%d must be even (a tile holds two points of one cloud)", d->N);
+        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: N=%d must be a multiple of %d (a tile holds %d points of one cloud)", d->N,
+                    pts, pts);
+    }
+    if (d->N < d->k) return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: N=%d < k=%d", d->N, d->k);
+    int lds = (32 * (d->D + 4) + 32 + 32 * 12) * (int)sizeof(float);
     lds += dev_switches().pair_lds_pad;                               // dev: force 1 workgroup per CU
-    const void* kern;
-    switch (heads) {
-        case 1: kern = reinterpret_cast<const void*>(pt_attn_pair_kernel<512>); break;
-        case 2: kern = reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<2>); break;
-        case 4: kern = reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<4>); break;
-        case 8: kern = reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<8>); break;
-        default: return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d (1, 2, 4, 8 are instantiated)", d->heads);
+    const dim3 grid((p.BN + pts - 1) / pts);
+    int rc = PTT_OK;
+    if (heads == 1) {
+#define PTT_PAIR_CASE(DV, KV)                                                                                        \
+        if (d->D == DV && d->k == KV) {                                                                              \
+            if ((rc = set_lds_limit(reinterpret_cast<const void*>(pt_attn_pair_kernel<DV, KV>), lds))) return rc;    \
+            hipLaunchKernelGGL((pt_attn_pair_kernel<DV, KV>), grid, dim3(256), lds, as_stream(stream), p);           \
+        }
+        PTT_PAIR_SHAPES(PTT_PAIR_CASE)
+#undef PTT_PAIR_CASE
+        return check_launch("pt_attn_pair_kernel");
     }
-    int rc = set_lds_limit(kern, lds);
-    if (rc) return rc;
-    const dim3 grid((p.BN + 1) / 2);
-    switch (heads) {
-        case 1: hipLaunchKernelGGL((pt_attn_pair_kernel<512>), grid, dim3(256), lds, as_stream(stream), p); break;
-        case 2: hipLaunchKernelGGL((pt_attn_pair_heads_kernel<2>), grid, dim3(256), lds, as_stream(stream), p); break;
-        case 4: hipLaunchKernelGGL((pt_attn_pair_heads_kernel<4>), grid, dim3(256), lds, as_stream(stream), p); break;
-        default: hipLaunchKernelGGL((pt_attn_pair_heads_kernel<8>), grid, dim3(256), lds, as_stream(stream), p); break;
+#define PTT_PAIR_HEADS(HV)                                                                                           \
+    if (heads == HV) {                                                                                               \
+        if ((rc = set_lds_limit(reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<HV>), lds))) return rc;      \
+        hipLaunchKernelGGL((pt_attn_pair_heads_kernel<HV>), grid, dim3(256), lds, as_stream(stream), p);             \
     }
-    return check_launch(heads == 1 ? "pt_attn_pair_kernel" : "pt_attn_pair_heads_kernel");
+    PTT_PAIR_HEADS(2) PTT_PAIR_HEADS(4) PTT_PAIR_HEADS(8)
+#undef PTT_PAIR_HEADS
+    return check_launch("pt_attn_pair_heads_kernel");
 }

@@ -1,40 +1,54 @@
-// Body of the Point-Transformer pair kernels (mfma_ops.hip: pt_attn_pair_kernel<D>, pt_attn_pair_heads_kernel<HEADS>),
-// included inside both kernel definitions with D, HEADS and `AttnParams p` in scope. Written out in each kernel instead of
+// Body of the Point-Transformer pair kernels (mfma_ops.hip: pt_attn_pair_kernel<D, KNN>, pt_attn_pair_heads_kernel<HEADS>),
+// included inside both kernel definitions with D, KNN, HEADS and `AttnParams p` in scope. Written out in each kernel instead of
 // called as an inlined device function: the single-head kernel then compiles to exactly the instructions it had before
 // the multi-head form existed (an inlined body is optimised before it meets the kernel's attributes and comes out
 // differently scheduled). Not a header to include anywhere else.
-    constexpr int KNN = 16, NT = D / 32, CT = NT / 4, LDK = D + 4, NKB = D / 8;
+// A 32-row tile holds PTS = 32 / KNN whole points (4 / 2 / 1 at 8 / 16 / 32 neighbours). With tile_row(r, half) =
+// (r & 3) + 8 (r >> 2) + 4 half, accumulator register r of EVERY lane belongs to point r / G, G = KNN / 2, and each point's
+// rows lie half in each half-wave: the softmax is PTS groups of G registers closed by one max_halves / add_halves.
+    static_assert(KNN == 8 || KNN == 16 || KNN == 32, "a 32-row tile splits into whole points");
+    static_assert(D % 128 == 0, "4 waves x 32 columns per column-tile round");
+    constexpr int NT = D / 32, CT = NT / 4, LDK = D + 4, NKB = D / 8;
+    constexpr int PTS = 32 / KNN, G = KNN / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;                                       // [32][LDK]
     int* nb = reinterpret_cast<int*>(smem + 32 * LDK);      // [32] flat neighbour row (b*N + n)
     constexpr int LDR = 12;                                 // [rel.x rel.y rel.z 1 | 0 0 0 0] + pad (stride = 4 mod 8)
     float* relt = smem + 32 * LDK + 32;                     // [32][LDR]: the A operand of fc_delta[0]
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, half = lane >> 5;
-    const int slot0 = logical_block() * 2;                   // the tile's two point slots
-    const int npts = min(2, p.BN - slot0);
-    // the points behind the slots (ptt_spatial_order_f32: neighbours in space next to each other in launch order); both lie in
-    // the same cloud (N is even, the order permutes inside clouds)
-    const int s0 = slot0 < p.BN ? slot0 : p.BN - 1, s1 = slot0 + 1 < p.BN ? slot0 + 1 : p.BN - 1;
-    const int pt0 = p.order ? p.order[s0] : s0, pt1 = p.order ? p.order[s1] : s1;
+    const int slot0 = logical_block() * PTS;                 // the tile's PTS point slots
+    const int npts = min(PTS, p.BN - slot0);
+    // the points behind the slots (ptt_spatial_order_f32: neighbours in space next to each other in launch order); all lie in
+    // the same cloud (N % PTS == 0, the order permutes inside clouds)
+    // (scalars chosen by constant conditions, not arrays filled in loops: at KNN = 16 this is, token for token, what the kernel
+    //  was compiled from before KNN became a parameter — an array form comes out differently scheduled)
+#define PTT_SLOT(i) (slot0 + (i) < p.BN ? slot0 + (i) : p.BN - 1)
+    const int s0 = slot0 < p.BN ? slot0 : p.BN - 1, s1 = PTS > 1 ? PTT_SLOT(1) : s0;
+    const int s2 = PTS > 2 ? PTT_SLOT(2) : s0, s3 = PTS > 2 ? PTT_SLOT(3) : s0;
+#undef PTT_SLOT
+    const int pt0 = p.order ? p.order[s0] : s0, pt1 = PTS > 1 ? (p.order ? p.order[s1] : s1) : pt0;
+    const int pt2 = PTS > 2 ? (p.order ? p.order[s2] : s2) : pt0, pt3 = PTS > 2 ? (p.order ? p.order[s3] : s3) : pt0;
+    const int pt[4] = {pt0, pt1, pt2, pt3};                 // indexed by unrolled loop counters only
     f32x4 pre[CT];
     prefetch_first_block_full<CT>(p.Wd1p, w, lane, pre);    // fc_delta[0]'s only weight block: requested first
     stagger_second_slot(p.first_wave, p.stagger);
     PTT_STAMP(0);
 
     if (t < 32) {
-        const int pt = (t >> 4) ? pt1 : pt0;
-        const int b = pt / p.N;
-        const int n = p.knn[(size_t)pt * KNN + (t & 15)];
+        // row t: point t / KNN of the tile, neighbour t % KNN
+        const int me = PTS == 1 ? pt0 : PTS == 2 ? ((t >> 4) ? pt1 : pt0) : ((t >> 4) ? ((t & 8) ? pt3 : pt2) : ((t & 8) ? pt1 : pt0));
+        const int b = me / p.N;
+        const int n = p.knn[(size_t)me * KNN + (t & (KNN - 1))];
         const int flat = b * p.N + n;
         nb[t] = n * (3 * D * (int)sizeof(float));      // byte offset of the neighbour's q|k|v row inside its cloud
         f32x4 r4;
         if (p.rel) {                                   // precomputed by the kNN kernel: no index -> xyz dependency
-            const float* rl = p.rel + ((size_t)pt * KNN + (t & 15)) * 3;
+            const float* rl = p.rel + ((size_t)me * KNN + (t & (KNN - 1))) * 3;
             r4 = f32x4{rl[0], rl[1], rl[2], 1.f};
         } else {
-            r4 = f32x4{p.xyz[(size_t)pt * 3 + 0] - p.xyz[(size_t)flat * 3 + 0],
-                       p.xyz[(size_t)pt * 3 + 1] - p.xyz[(size_t)flat * 3 + 1],
-                       p.xyz[(size_t)pt * 3 + 2] - p.xyz[(size_t)flat * 3 + 2], 1.f};
+            r4 = f32x4{p.xyz[(size_t)me * 3 + 0] - p.xyz[(size_t)flat * 3 + 0],
+                       p.xyz[(size_t)me * 3 + 1] - p.xyz[(size_t)flat * 3 + 1],
+                       p.xyz[(size_t)me * 3 + 2] - p.xyz[(size_t)flat * 3 + 2], 1.f};
         }
         *reinterpret_cast<f32x4*>(relt + t * LDR) = r4;
         *reinterpret_cast<f32x4*>(relt + t * LDR + 4) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -76,7 +90,7 @@
     // Gathers of neighbour k / v rows: raw buffer loads on a descriptor based at the cloud's first q|k|v row. The
     // per-(row, lane) byte offset is ONE 32-bit VGPR per tile row; channel group and the k / v column block are
     // immediates or an SGPR — a flat 64-bit address per load costs 3-4 vector-ALU instructions, 64 loads per phase.
-    const int cloud = pt0 / p.N;
+    const int cloud = pt[0] / p.N;
     const __amdgpu_buffer_rsrc_t rq = weight_rsrc(p.qkv + (size_t)cloud * p.N * 3 * D);
     int nrow[16];  // byte offset of (neighbour row, this lane's first column) for each of this lane's 16 tile rows
 #pragma unroll
@@ -85,16 +99,19 @@
     lds_barrier();  // all waves done with h
     // t = (q_i - k_j) + delta  -> X
     {
-        const int pa = pt0, pb = (npts > 1) ? pt1 : pt0;
+        // a slot past the last point reads the tile's first point
+        const int pa = pt0, pb = (npts > 1) ? pt1 : pt0, pc = (npts > 2) ? pt2 : pt0, pd = (npts > 3) ? pt3 : pt0;
 #pragma unroll
         for (int u = 0; u < CT; ++u) {
             const float qa = p.qkv[(size_t)pa * 3 * D + cols[u]];
-            const float qb = p.qkv[(size_t)pb * 3 * D + cols[u]];
+            const float qb = PTS > 1 ? p.qkv[(size_t)pb * 3 * D + cols[u]] : qa;
+            const float qc = PTS > 2 ? p.qkv[(size_t)pc * 3 * D + cols[u]] : qa;
+            const float qd = PTS > 2 ? p.qkv[(size_t)pd * 3 * D + cols[u]] : qa;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float kv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                     rq, nrow[r] + (D + u * 128) * (int)sizeof(float), 0, 0));
-                const float q = (r < 8) ? qa : qb;
+                const float q = PTS == 1 ? qa : PTS == 2 ? ((r < 8) ? qa : qb) : ((r < 8) ? ((r < 4) ? qa : qb) : ((r < 12) ? qc : qd));
                 Xs[tile_row(r, half) * LDK + cols[u]] = (q - kv) + delta[0][u][r];
             }
         }
@@ -124,7 +141,7 @@
         lds_barrier();
     }
 
-    // ---- a = fc_gamma[2](g); softmax over the 16 neighbours; res = sum attn * (v + delta) ----
+    // ---- a = fc_gamma[2](g); softmax over the KNN neighbours; res = sum attn * (v + delta) ----
     f32x16 acc[1][CT];
     zero_acc(acc);
     PTT_STAMP(5);
@@ -133,12 +150,12 @@
     else
         gemm_heads<D, HEADS>(Xs, LDK, p.Wg2p, w, lane, acc, pre);
     PTT_STAMP(6);
-    // softmax_j((a_j + b) / sqrt(D)) over the 16 neighbours of a point: the bias b is the same for every neighbour, so
+    // softmax_j((a_j + b) / sqrt(D)) over the KNN neighbours of a point: the bias b is the same for every neighbour, so
     // it cancels (fc_gamma[2].bias is never read); 1/sqrt(D) and log2(e) are one constant inside exp2; the weighted sum
     // is normalised once at the end. Fewer vector-ALU instructions next to the other workgroup's MFMA stream.
     const float kexp = 1.4426950408889634f / sqrtf((float)(D / HEADS));     // multi-head: 1 / sqrt(hd)
-    // all 64 neighbour values of this lane are requested before any softmax arithmetic: one L2 round trip
-    // instead of eight (the gathers, not the math, were the length of this phase)
+    // all 16 CT neighbour values of this lane are requested before any softmax arithmetic: one L2 round trip
+    // instead of 2 CT (the gathers, not the math, were the length of this phase)
     float vv[CT][16];
 #pragma unroll
     for (int u = 0; u < CT; ++u)
@@ -149,16 +166,16 @@
 #pragma unroll
     for (int u = 0; u < CT; ++u) {
 #pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            float s[8];
-            float m = acc[0][u][pp * 8];
+        for (int pp = 0; pp < PTS; ++pp) {
+            float s[G];
+            float m = acc[0][u][pp * G];
 #pragma unroll
-            for (int r = 1; r < 8; ++r) m = fmaxf(m, acc[0][u][pp * 8 + r]);
+            for (int r = 1; r < G; ++r) m = fmaxf(m, acc[0][u][pp * G + r]);
             m = max_halves(m);
             float sum = 0.f, o = 0.f;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int rr = pp * 8 + r;
+            for (int r = 0; r < G; ++r) {
+                const int rr = pp * G + r;
                 s[r] = __builtin_amdgcn_exp2f((acc[0][u][rr] - m) * kexp);
                 sum += s[r];
                 o += s[r] * (vv[u][rr] + delta[0][u][rr]);
@@ -168,19 +185,19 @@
             const float rsum = __builtin_amdgcn_rcpf(sum);
             if (p.attn && pp < npts) {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int row = tile_row(pp * 8 + r, half);  // = pp*16 + j
+                for (int r = 0; r < G; ++r) {
+                    const int row = tile_row(pp * G + r, half);  // = pp*KNN + j
                     if constexpr (HEADS == 1) {
-                        p.attn[((size_t)(pp ? pt1 : pt0) * KNN + (row & 15)) * D + cols[u]] = s[r] * rsum;
+                        p.attn[((size_t)pt[pp] * KNN + (row & (KNN - 1))) * D + cols[u]] = s[r] * rsum;
                     } else {                                     // the reference's (B*heads, N, k, hd) layout
                         constexpr int HD = D / HEADS;
-                        const int pt = pp ? pt1 : pt0, b = pt / p.N, n = pt - b * p.N;
-                        p.attn[((((size_t)b * HEADS + cols[u] / HD) * p.N + n) * KNN + (row & 15)) * HD + cols[u] % HD] =
+                        const int b = pt[pp] / p.N, n = pt[pp] - b * p.N;
+                        p.attn[((((size_t)b * HEADS + cols[u] / HD) * p.N + n) * KNN + (row & (KNN - 1))) * HD + cols[u] % HD] =
                             s[r] * rsum;
                     }
                 }
             }
-            if (half == 0 && pp < npts) p.res[(size_t)(pp ? pt1 : pt0) * D + cols[u]] = o * rsum;
+            if (half == 0 && pp < npts) p.res[(size_t)pt[pp] * D + cols[u]] = o * rsum;
         }
     }
     PTT_STAMP(7);

@@ -1897,10 +1897,19 @@ extern "C" int ptt_scatter_rows_csr_sub_f32(const float* g, const int32_t* order
 
 static int pt_train_check(const char* what, int B, int N, int k, int D, const void* p0, const void* p1, const void* p2, const void* p3) {
     if (B < 0 || N <= 0 || D <= 0 || (D & 3)) return fail(PTT_EINVAL, "%s: B=%d N=%d D=%d (D %% 4)", what, B, N, D);
-    if (k != 16) return fail(PTT_EUNSUPPORTED, "%s: k=%d (16 neighbours is instantiated)", what, k);
+    if (k != 8 && k != 16 && k != 32) return fail(PTT_EUNSUPPORTED, "%s: k=%d (8, 16 and 32 neighbours are instantiated)", what, k);
     if (B > 0 && (!p0 || !p1 || !p2 || !p3)) return fail(PTT_EINVAL, "%s: null pointer", what);
     return PTT_OK;
 }
+
+// one of the element-wise pair kernels at the neighbour count pt_train_check let through
+#define PTT_PAIR_EW(KERNEL, ...)                                                                                                 \
+    do {                                                                                                                         \
+        const dim3 g_(ew_grid((size_t)pts * (D >> 2)));                                                                          \
+        if (k == 8) hipLaunchKernelGGL((KERNEL<8>), g_, dim3(256), 0, as_stream(stream), __VA_ARGS__);                           \
+        else if (k == 16) hipLaunchKernelGGL((KERNEL<16>), g_, dim3(256), 0, as_stream(stream), __VA_ARGS__);                    \
+        else hipLaunchKernelGGL((KERNEL<32>), g_, dim3(256), 0, as_stream(stream), __VA_ARGS__);                                 \
+    } while (0)
 
 extern "C" int ptt_pt_pair_input_f32(const float* q, const float* kf, const int32_t* knn, const float* pos, int B, int N, int k,
                                      int D, float* t, ptt_stream_t stream) {
@@ -1908,7 +1917,7 @@ extern "C" int ptt_pt_pair_input_f32(const float* q, const float* kf, const int3
     if (B == 0) return PTT_OK;
     if (!t) return fail(PTT_EINVAL, "ptt_pt_pair_input_f32: null pointer");
     const long long pts = (long long)B * N;
-    hipLaunchKernelGGL((pair_input_kernel<16>), dim3(ew_grid((size_t)pts * (D >> 2))), dim3(256), 0, as_stream(stream), q, kf, knn, pos, N,
+    PTT_PAIR_EW(pair_input_kernel, q, kf, knn, pos, N,
                        D, pts, t, D, D);
     return check_launch("pair_input_kernel");
 }
@@ -1923,7 +1932,7 @@ extern "C" int ptt_pt_pair_input_ld_f32(const float* q, int ldq, const float* kf
     if (B == 0) return PTT_OK;
     if (!t) return fail(PTT_EINVAL, "ptt_pt_pair_input_ld_f32: null pointer");
     const long long pts = (long long)B * N;
-    hipLaunchKernelGGL((pair_input_kernel<16>), dim3(ew_grid((size_t)pts * (D >> 2))), dim3(256), 0, as_stream(stream), q, kf, knn, pos, N,
+    PTT_PAIR_EW(pair_input_kernel, q, kf, knn, pos, N,
                        D, pts, t, ldq, ldk);
     return check_launch("pair_input_kernel");
 }
@@ -1935,7 +1944,7 @@ extern "C" int ptt_pt_attn_fwd_ld_f32(const float* a, const float* vf, int ldv, 
     if (B == 0) return PTT_OK;
     if (!res) return fail(PTT_EINVAL, "ptt_pt_attn_fwd_ld_f32: null pointer");
     const long long pts = (long long)B * N;
-    hipLaunchKernelGGL((attn_fwd_kernel<16>), dim3(ew_grid((size_t)pts * (D >> 2))), dim3(256), 0, as_stream(stream), a, vf, knn, pos, N, D,
+    PTT_PAIR_EW(attn_fwd_kernel, a, vf, knn, pos, N, D,
                        pts, scale, attn, res, ldv);
     return check_launch("attn_fwd_kernel");
 }
@@ -1946,7 +1955,7 @@ extern "C" int ptt_pt_attn_train_fwd_f32(const float* a, const float* vf, const 
     if (B == 0) return PTT_OK;
     if (!attn || !res) return fail(PTT_EINVAL, "ptt_pt_attn_train_fwd_f32: null pointer");
     const long long pts = (long long)B * N;
-    hipLaunchKernelGGL((attn_fwd_kernel<16>), dim3(ew_grid((size_t)pts * (D >> 2))), dim3(256), 0, as_stream(stream), a, vf, knn, pos, N, D,
+    PTT_PAIR_EW(attn_fwd_kernel, a, vf, knn, pos, N, D,
                        pts, scale, attn, res, D);
     return check_launch("attn_fwd_kernel");
 }
@@ -1957,10 +1966,12 @@ extern "C" int ptt_pt_attn_train_bwd_f32(const float* attn, const float* vf, con
     if (B == 0) return PTT_OK;
     if (!dres || !da || !dvp) return fail(PTT_EINVAL, "ptt_pt_attn_train_bwd_f32: null pointer");
     const long long pts = (long long)B * N;
-    hipLaunchKernelGGL((attn_bwd_kernel<16>), dim3(ew_grid((size_t)pts * (D >> 2))), dim3(256), 0, as_stream(stream), attn, vf, knn, pos,
+    PTT_PAIR_EW(attn_bwd_kernel, attn, vf, knn, pos,
                        dres, N, D, pts, scale, da, dvp);
     return check_launch("attn_bwd_kernel");
 }
+
+#undef PTT_PAIR_EW
 
 static inline bool wgrad_smallk_ok(int Cout, int Cin) { return Cin >= 1 && Cin <= 4 && (Cout & 3) == 0; }
 

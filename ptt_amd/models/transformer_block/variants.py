@@ -40,6 +40,7 @@ def _rows2d(layers, x):
 
 
 SPATIAL_ORDER_MIN_POINTS = 512       # clouds from this size on are handed to the pair kernel in Morton order
+FUSED_D_MODEL, FUSED_KNN = (128, 256, 512), (8, 16, 32)      # what ptt_pt_attn_pair_f32 instantiates for one head
 
 
 class TransformerBlock(nn.Module):
@@ -59,17 +60,19 @@ class TransformerBlock(nn.Module):
 
     # ---------------------------------------------------------------- fused-path parameters
     def _fusable(self, xyz, features):
-        """Eval mode on a HIP device, the instantiated shape (d_model 512, k 16, an even number of points) and no
-        autograd graph being recorded; an eval-mode HIP call that is turned away says so once (ops.note_unfused)."""
+        """Eval mode on a HIP device, an instantiated shape (d_model 128 / 256 / 512, k 8 / 16 / 32, a number of points >= k
+        that is a multiple of the 32 // k points of a kernel tile) and no autograd graph being recorded; an eval-mode HIP
+        call that is turned away says so once (ops.note_unfused)."""
         if self.training or not xyz.is_cuda:
             return False
         name = 'TransformerBlock(d_model=%d, k=%d)' % (self.d_model, self.k)
         if ops.autograd_recording(self, xyz, features):
             return ops.note_unfused(name, 'autograd is recording (wrap inference in torch.no_grad())')
-        if self.d_model != 512 or self.k != 16:
-            return ops.note_unfused(name, 'ptt_pt_attn_pair_f32 instantiates d_model 512, k 16')
-        if xyz.shape[1] % 2 != 0 or xyz.shape[1] < self.k:
-            return ops.note_unfused(name, 'needs an even number of points >= k (got %d)' % xyz.shape[1])
+        if self.d_model not in FUSED_D_MODEL or self.k not in FUSED_KNN:
+            return ops.note_unfused(name, 'ptt_pt_attn_pair_f32 instantiates d_model 128, 256, 512 and k 8, 16, 32')
+        if xyz.shape[1] % (32 // self.k) != 0 or xyz.shape[1] < self.k:
+            return ops.note_unfused(name, 'needs a number of points >= k that is a multiple of %d (got %d)'
+                                    % (32 // self.k, xyz.shape[1]))
         if features.dtype != torch.float32 or xyz.dtype != torch.float32:
             return ops.note_unfused(name, 'inputs must be float32')
         return True
@@ -111,7 +114,9 @@ class TransformerBlock(nn.Module):
                 knn_idx, rel = knn
             else:
                 knn_idx, rel = ops.knn(xyz, self.k, want_rel=True)
-            if xyz.shape[0] * xyz.shape[1] <= PER_LAYER_MAX_POINTS and not want_attn:
+            # the per-layer forms below have 16 neighbours and the 512-wide layout built in (rowjobs.hip, prologue 2 / epilogue 1)
+            per_layer = (D, self.k) == (512, 16) and xyz.shape[0] * xyz.shape[1] <= PER_LAYER_MAX_POINTS
+            if per_layer and not want_attn:
                 # a handful of frames (one tracklet frame: 128 / 64 points): the fused pair kernel's one workgroup per two
                 # points is a 64-workgroup launch of three chained 512 x 512 GEMMs (106 us on 64 of the 256 CUs). Per layer,
                 # each GEMM over the (point, neighbour) rows fills the chip, and the element-wise steps between them ride in
@@ -138,7 +143,7 @@ class TransformerBlock(nn.Module):
                 ops.row_jobs([ops.row_job(P['fc2'], self.d_points, x=res, shift=P['fc2_b'], res=features, out=out)])
                 return out, None
             qkv = ops.linear(features, P['qkv'], 3 * D, None, P['qkv_b'])
-            if xyz.shape[0] * xyz.shape[1] <= PER_LAYER_MAX_POINTS:
+            if per_layer:
                 # the same per-layer form with the (B,N,k,D) attention tensor written out
                 pairs = rel.view(-1, 3)
                 h = ops.linear(pairs, P['wd1_lin'], D, None, P['bd1'], relu=True)

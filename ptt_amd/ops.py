@@ -657,6 +657,7 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
     """Fused per-(point,neighbour) part of TransformerBlock.forward (variants.py:158-163).
     wd1p = pack_delta0(fc_delta[0].weight, fc_delta[0].bias); the other weights from pack_weight. order: spatial_order(xyz) or
     None — which point every launch slot works on (the results do not depend on it).
+    One head: d_model 128 / 256 / 512 and k 8 / 16 / 32 neighbours, N >= k a multiple of 32 // k (ValueError otherwise).
     heads > 1 (2, 4, 8): MulHeadTransformerLayer's attention (multitransformer.py:46-56) — wg1p / wg2p are the packed
     hd x hd fc_gamma weights every head shares (hd = d_model / heads), bg1 is fc_gamma[0].bias repeated `heads` times.
     Returns (res (B,N,D), attn | None): attn (B,N,k,D), or (B*heads,N,k,hd) when heads > 1."""
@@ -666,6 +667,14 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
     B, N, _ = xyz.shape
     k = knn_idx.shape[2]
     D = int(d_model)
+    # what ptt_pt_attn_pair_f32 instantiates (include/ptt_hip.h): said here before anything is allocated
+    if D not in (128, 256, 512) or k not in (8, 16, 32) or (heads > 1 and (D, k) != (512, 16)):
+        raise ValueError("pt_attn_pair: d_model=%d k=%d heads=%d (one head: d_model 128, 256, 512 x k 8, 16, 32; several heads: "
+                         "d_model 512, k 16)" % (D, k, heads))
+    if N % (32 // k) != 0 or N < k:
+        raise ValueError("pt_attn_pair: N=%d must be a multiple of %d (the points of a 32-row tile) and >= k=%d" % (N, 32 // k, k))
+    if tuple(knn_idx.shape[:2]) != (B, N) or tuple(qkv.shape) != (B, N, 3 * D):
+        raise ValueError("pt_attn_pair: knn_idx (B,N,k) and qkv (B,N,3*d_model) expected")
     res = torch.empty((B, N, D), dtype=torch.float32, device=xyz.device)
     ashape = (B, N, k, D) if heads == 1 else (B * heads, N, k, D // heads)
     attn = torch.empty(ashape, dtype=torch.float32, device=xyz.device) if want_attn else None

@@ -986,7 +986,7 @@ def attn_core(fc_gamma, q, kf, vf, knn, pos, scale, order, start, heads=1):
 
 
 def pt_block_usable(block, xyz, features):
-    return (block.training and xyz.is_cuda and features.dtype == torch.float32 and block.k == 16 and block.d_model % 4 == 0
+    return (block.training and xyz.is_cuda and features.dtype == torch.float32 and block.k in (8, 16, 32) and block.d_model % 4 == 0
             and xyz.shape[1] * block.k <= 16384)
 
 
