@@ -49,6 +49,14 @@ const DevSwitches& dev_switches();
 // call this on every launch and it is a table lookup after the first.
 int set_lds_limit(const void* fn, int bytes);
 
+// A launch with `lds` bytes of dynamic LDS: raise the kernel's limit, launch, report a launch error under `name`.
+template <class K, class... Args>
+int launch(const char* name, K kernel, dim3 grid, dim3 block, int lds, hipStream_t s, const Args&... args) {
+    if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return check_launch(name);
+}
+
 // wgrad_stream.hip: the weight gradient of narrow layers (Cin = 64, Cout = 64 / 128) over many rows, partial[chunk][Cout][Cin]
 bool wgrad_stream_ok(int R, int Cout, int Cin, int ldz, int ldx);
 int wgrad_stream_rows(int R);

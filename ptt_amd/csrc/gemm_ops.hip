@@ -15,41 +15,20 @@
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "mfma_common.h"
 
 namespace ptt {
 
-typedef float g32x16 __attribute__((ext_vector_type(16)));
-typedef float g32x4 __attribute__((ext_vector_type(4)));
 typedef int gi32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int gu32x4 __attribute__((__vector_size__(4 * sizeof(unsigned int))));
 
 namespace {
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t g_rsrc(const void* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);   // raw, 32-bit offsets
-}
-__device__ __forceinline__ g32x4 g_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(g32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
 __device__ __forceinline__ float g_load1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 __device__ __forceinline__ void g_store1(float v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, voff, soff, 0);
-}
-// workgroup barrier that orders LDS traffic only (global loads / stores stay in flight across it)
-__device__ __forceinline__ void g_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ int g_tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-// lane <-> lane^32 sum on v_permlane32_swap (inline asm: hipcc folds the builtin when both operands are equal)
-__device__ __forceinline__ float g_add_halves(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return a + b;
 }
 // (value, row) of lane ^ 32 beside this lane's: lo = the lower half-wave's pair in both halves, hi = the upper half-wave's
 __device__ __forceinline__ void g_swap_pair(float v, int i, float& lo_v, int& lo_i, float& hi_v, int& hi_i) {
@@ -58,12 +37,6 @@ __device__ __forceinline__ void g_swap_pair(float v, int i, float& lo_v, int& lo
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(c), "+v"(d));
     lo_v = a; hi_v = b; lo_i = c; hi_i = d;
-}
-// the dispatcher places block b on XCD b % 8: consecutive LOGICAL blocks share an XCD (and its L2)
-__device__ __forceinline__ int g_logical_block() {
-    const int bid = blockIdx.x, per = (int)gridDim.x >> 3;
-    if (bid >= (per << 3)) return bid;
-    return (bid & 7) * per + (bid >> 3);
 }
 
 }  // namespace
@@ -128,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
     const int t = threadIdx.x, lane = t & 63, half = lane >> 5, col = lane & 31;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wr = w / WC, wc = w % WC;
-    const int lb = g_logical_block();
+    const int lb = logical_block();
     const int cg = lb % p.ncg, g = lb / p.ncg;
     if (g >= p.ntiles) return;
     const int ntw = (p.ntiles - g + p.G - 1) / p.G;             // this workgroup's tiles: g, g + G, ...
@@ -138,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
     // address is in the VGPR offset, which the range check covers; the chunk part in the scalar offset never leaves a row)
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X), 0,
                                                                          ((p.rows - 1) * p.ldx + p.K) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = g_rsrc(p.Wp), ro = g_rsrc(p.out);
+    const __amdgpu_buffer_rsrc_t rw = weight_rsrc(p.Wp), ro = weight_rsrc(p.out);
     const int ct0 = cg * (WC * CT) + wc;
     // HD: the head of this workgroup's columns; its first input channel (bytes) and its column tiles inside the shared weight
     const int head = HD ? (cg * (WC * CT * 32)) / p.hd : 0;
@@ -154,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
     const int slot_off = r0 * ldx4 + q * 16;                    // + i * RSTEP * ldx4 + tile * TR * ldx4 bytes
     const int tile_bytes = TR * ldx4;
 
-    g32x16 acc[RT][CT];
+    f32x16 acc[RT][CT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -165,16 +138,16 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
 #pragma unroll
     for (int u = 0; u < CT; ++u) { dsum[u] = 0.0; dsq[u] = 0.0; }
 
-    g32x4 st[SLOTS];
-    g32x4 ta = {1.f, 1.f, 1.f, 1.f}, tb = {0.f, 0.f, 0.f, 0.f};
+    f32x4 st[SLOTS];
+    f32x4 ta = {1.f, 1.f, 1.f, 1.f}, tb = {0.f, 0.f, 0.f, 0.f};
     // AIN: z beside the gradient (AIN 2) / the pooled gradient and the arg-max of the row's group beside z (AIN 3), the five
     // per-channel constants of the chunk, and where the staged dz goes when this workgroup writes it out
     constexpr bool PIN = AIN >= 16;                             // pooled gradient
     constexpr int TS = AIN == 2 ? SLOTS : 1, NG = PIN ? TR / AIN : 1, SPG = SLOTS / NG;      // slots of a thread per group
     static_assert(!PIN || (TR % AIN == 0 && AIN % (256 / QPR) == 0 && SLOTS % NG == 0), "a thread's slots fall into whole groups");
-    g32x4 sz[TS], sg[NG];
+    f32x4 sz[TS], sg[NG];
     gi32x4 sarg[NG];
-    g32x4 tk1 = {0.f, 0.f, 0.f, 0.f}, tc0 = tk1, tc1 = tk1, tmu = tk1;
+    f32x4 tk1 = {0.f, 0.f, 0.f, 0.f}, tc0 = tk1, tc1 = tk1, tmu = tk1;
     int aout_off = 0;
     const bool write_a = AIN != 0 && p.a_out != nullptr && cg == 0;
     const __amdgpu_buffer_rsrc_t rtz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AIN == 2 ? p.tz : p.X), 0,
@@ -191,16 +164,16 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
         const int tcl = tile < p.ntiles ? tile : p.ntiles;
         const int tb_off = tcl * tile_bytes + slot_off;
 #pragma unroll
-        for (int i = 0; i < SLOTS; ++i) st[i] = g_load4(rx, tb_off + i * (RSTEP * ldx4), c * (KC * 4) + xk0);
+        for (int i = 0; i < SLOTS; ++i) st[i] = weight_load(rx, tb_off + i * (RSTEP * ldx4), c * (KC * 4) + xk0);
         if (ACT || AIN) {
-            ta = *reinterpret_cast<const g32x4*>(p.in_a + c * KC + 4 * q);
-            tb = *reinterpret_cast<const g32x4*>(p.in_b + c * KC + 4 * q);
+            ta = *reinterpret_cast<const f32x4*>(p.in_a + c * KC + 4 * q);
+            tb = *reinterpret_cast<const f32x4*>(p.in_b + c * KC + 4 * q);
         }
         if constexpr (AIN != 0) {
-            tk1 = *reinterpret_cast<const g32x4*>(p.tk1 + c * KC + 4 * q);
-            tc0 = *reinterpret_cast<const g32x4*>(p.tc0 + c * KC + 4 * q);
-            tc1 = *reinterpret_cast<const g32x4*>(p.tc1 + c * KC + 4 * q);
-            tmu = *reinterpret_cast<const g32x4*>(p.tmu + c * KC + 4 * q);
+            tk1 = *reinterpret_cast<const f32x4*>(p.tk1 + c * KC + 4 * q);
+            tc0 = *reinterpret_cast<const f32x4*>(p.tc0 + c * KC + 4 * q);
+            tc1 = *reinterpret_cast<const f32x4*>(p.tc1 + c * KC + 4 * q);
+            tmu = *reinterpret_cast<const f32x4*>(p.tmu + c * KC + 4 * q);
             // row part AND chunk part in the vector offset, no scalar offset: a 128-bit buffer store WITH an SGPR offset showed the
             // "store data overwritten by the next VALU instruction" hazard on gfx950 (element 1 of a quad, lanes 12-15 of every 16,
             // one launch in a few) that hipcc only guards against for stores WITHOUT one (scripts/probes/fused_bnbwd_probe.py);
@@ -210,25 +183,25 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
         if constexpr (AIN == 2) {
             const int z_off = (tcl * TR + r0) * (p.ldtz * 4) + q * 16;
 #pragma unroll
-            for (int i = 0; i < SLOTS; ++i) sz[i] = g_load4(rtz, z_off + i * (RSTEP * p.ldtz * 4), c * (KC * 4));
+            for (int i = 0; i < SLOTS; ++i) sz[i] = weight_load(rtz, z_off + i * (RSTEP * p.ldtz * 4), c * (KC * 4));
         }
         if constexpr (PIN) {        // slot i lies in group i / SPG of the tile (RSTEP divides the group size, r0 < RSTEP)
 #pragma unroll
             for (int gq = 0; gq < NG; ++gq) {
                 const int grp = tcl * NG + gq;
-                sg[gq] = g_load4(rtg, grp * (p.ldtg * 4) + q * 16, c * (KC * 4));
-                sarg[gq] = __builtin_bit_cast(gi32x4, g_load4(rta, grp * (p.K * 4) + q * 16, c * (KC * 4)));
+                sg[gq] = weight_load(rtg, grp * (p.ldtg * 4) + q * 16, c * (KC * 4));
+                sarg[gq] = __builtin_bit_cast(gi32x4, weight_load(rta, grp * (p.K * 4) + q * 16, c * (KC * 4)));
             }
         }
     };
     auto stage = [&](float* buf, int i) {                       // deferred BatchNorm + ReLU of the producing layer, LDS write
-        g32x4 v = st[i];
+        f32x4 v = st[i];
         if (ACT) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = fmaxf(__builtin_fmaf(v[k], ta[k], tb[k]), 0.f);
         }
         if constexpr (AIN == 2) {
-            const g32x4 z = sz[i];
+            const f32x4 z = sz[i];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float t = __builtin_fmaf(tc1[k], z[k] - tmu[k], tc0[k]);
@@ -236,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
             }
         }
         if constexpr (PIN) {
-            const g32x4 z = v, gp = sg[i / SPG];
+            const f32x4 z = v, gp = sg[i / SPG];
             const gi32x4 ar = sarg[i / SPG];
             const int srow = r0 + (i % SPG) * RSTEP;            // this slot's row inside its group
 #pragma unroll
@@ -245,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
                 v[k] = (ar[k] == srow && __builtin_fmaf(z[k], ta[k], tb[k]) > 0.f) ? __builtin_fmaf(tk1[k], gp[k], t) : t;
             }
         }
-        *reinterpret_cast<g32x4*>(buf + lds_slot + i * (RSTEP * LDK)) = v;
+        *reinterpret_cast<f32x4*>(buf + lds_slot + i * (RSTEP * LDK)) = v;
         if constexpr (AIN != 0) {
             if (write_a)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gu32x4, v), rao, aout_off + i * (RSTEP * p.lda_out * 4), 0, 0);
@@ -254,8 +227,8 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
 
     // bias / ReLU branch-free: a missing bias reads any valid address and is replaced by 0, no ReLU = floor -inf
     const bool has_bias = p.bias != nullptr;
-    const __amdgpu_buffer_rsrc_t rb = g_rsrc(has_bias ? p.bias : p.Wp);
-    const __amdgpu_buffer_rsrc_t rr = g_rsrc(p.residual ? p.residual : (p.mask ? p.mask : (p.bz ? p.bz : p.X)));
+    const __amdgpu_buffer_rsrc_t rb = weight_rsrc(has_bias ? p.bias : p.Wp);
+    const __amdgpu_buffer_rsrc_t rr = weight_rsrc(p.residual ? p.residual : (p.mask ? p.mask : (p.bz ? p.bz : p.X)));
     const int ldr = p.residual ? p.ldr : (p.mask ? p.ldm : p.ldbz);
     const float rfloor = p.relu ? 0.f : -__builtin_inff();
     auto epilogue = [&](int row_w, auto full_c, auto mode_c) {      // mode 0: plain, 1: + residual, 2: masked by `mask` > 0,
@@ -328,7 +301,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
                 if constexpr (GS == 16 && MODE == 1) {
 #pragma unroll
                     for (int gq = 0; gq < 2; ++gq) {            // the other half-wave holds the group's other eight rows
-                        const float tot = g_add_halves(gs[gq]);
+                        const float tot = add_halves(gs[gq]);
                         const int row_g = row_w + rt * 32 + gq * 16;
                         if (half == 0 && row_g < p.rows) p.gsum[(size_t)(row_g >> 4) * p.ldgs + cn] = tot;
                     }
@@ -373,14 +346,14 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
     // ---- prologue: the first unit is staged in the open ----
     int tile = g, c = 0;
     fetch(tile, c);
-    g32x4 wq[PD][CT];                                           // the weights of the current unit's first PD K-blocks
+    f32x4 wq[PD][CT];                                           // the weights of the current unit's first PD K-blocks
 #pragma unroll
     for (int k = 0; k < PD; ++k)
 #pragma unroll
-        for (int u = 0; u < CT; ++u) wq[k][u] = g_load4(rw, wvoff, k * wkstep + u * (WC * 1024));
+        for (int u = 0; u < CT; ++u) wq[k][u] = weight_load(rw, wvoff, k * wkstep + u * (WC * 1024));
 #pragma unroll
     for (int i = 0; i < SLOTS; ++i) stage(smem, i);
-    g_lds_barrier();
+    lds_barrier();
 
     for (int un = 0; un < nunits; ++un) {
         int c_n = c + 1, tile_n = tile;
@@ -389,26 +362,26 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
         float* nxt = smem + ((un + 1) & 1) * BUF;
         const int wk_cur = c * (NKB * wkstep), wk_nxt = c_n * (NKB * wkstep);
         const float* arow = cur + (wr * RT * 32 + (lane & 31)) * LDK + 4 * half;
-        g32x4 av[2][RT];
-        g32x4 wv[NKB + PD][CT];
+        f32x4 av[2][RT];
+        f32x4 wv[NKB + PD][CT];
 #pragma unroll
         for (int k = 0; k < PD; ++k)
 #pragma unroll
             for (int u = 0; u < CT; ++u) wv[k][u] = wq[k][u];
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) av[0][rt] = *reinterpret_cast<const g32x4*>(arow + rt * 32 * LDK);
+        for (int rt = 0; rt < RT; ++rt) av[0][rt] = *reinterpret_cast<const f32x4*>(arow + rt * 32 * LDK);
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
             {   // weight fragments PD K-blocks ahead; past the end of this unit they are the next unit's first ones
                 const int kq = kb + PD;
                 const int base = (EXP & 4) ? 0 : (kq < NKB ? wk_cur + kq * wkstep : wk_nxt + (kq - NKB) * wkstep);
 #pragma unroll
-                for (int u = 0; u < CT; ++u) wv[kq][u] = g_load4(rw, wvoff, base + u * (WC * 1024));
+                for (int u = 0; u < CT; ++u) wv[kq][u] = weight_load(rw, wvoff, base + u * (WC * 1024));
             }
             if (kb + 1 < NKB) {
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt)
-                    av[(kb + 1) & 1][rt] = *reinterpret_cast<const g32x4*>(arow + rt * 32 * LDK + (kb + 1) * 8);
+                    av[(kb + 1) & 1][rt] = *reinterpret_cast<const f32x4*>(arow + rt * 32 * LDK + (kb + 1) * 8);
             }
             if (kb == 0 && !(EXP & 2)) fetch(tile_n, c_n);      // the next unit's rows: in flight under this unit's MFMAs
             __builtin_amdgcn_sched_barrier(0);
@@ -449,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RowsGemmParams p) {
                 else epilogue(row_w, std::false_type(), M0());
             }
         }
-        if (!(EXP & 8)) g_lds_barrier();
+        if (!(EXP & 8)) lds_barrier();
         tile = tile_n; c = c_n;
     }
     if (STATS) {                                                // the two half-waves hold different rows of the same columns
@@ -488,18 +461,18 @@ __global__ __launch_bounds__(512, 1) void wgrad2_kernel(const float* __restrict_
     // quad twice): consecutive LOGICAL blocks share an XCD, so the tiles of a chunk meet in that XCD's L2 instead of each
     // fetching its operands from the fabric (profiles/r04z_pmc_train_gemm: 805 MB read per launch against 402 MB compulsory)
     const int ntile = (Cout / BN) * nbk;
-    const int lb = g_logical_block();
+    const int lb = logical_block();
     const int tile_id = lb % ntile, chunk = lb / ntile;
     const int bo = tile_id / nbk, bi = tile_id - bo * nbk;
     const int o0 = bo * BN, i0 = bi * BK;
     const int r_begin = chunk * chunk_rows, r_end = min(R, r_begin + chunk_rows);
-    const __amdgpu_buffer_rsrc_t rz = g_rsrc(dZ), rxx = g_rsrc(X);
+    const __amdgpu_buffer_rsrc_t rz = weight_rsrc(dZ), rxx = weight_rsrc(X);
     const int qa = t % QA, ra = t / QA, qb = t % QB, rb = t / QB;
     constexpr int RSA = 512 / QA, RSB = 512 / QB;
-    g32x4 ta = {1.f, 1.f, 1.f, 1.f}, tb = {0.f, 0.f, 0.f, 0.f};
-    if (xa) { ta = *reinterpret_cast<const g32x4*>(xa + i0 + 4 * qb); tb = *reinterpret_cast<const g32x4*>(xb + i0 + 4 * qb); }
+    f32x4 ta = {1.f, 1.f, 1.f, 1.f}, tb = {0.f, 0.f, 0.f, 0.f};
+    if (xa) { ta = *reinterpret_cast<const f32x4*>(xa + i0 + 4 * qb); tb = *reinterpret_cast<const f32x4*>(xb + i0 + 4 * qb); }
 
-    g32x16 acc[TN][TK];
+    f32x16 acc[TN][TK];
 #pragma unroll
     for (int a = 0; a < TN; ++a)
 #pragma unroll
@@ -510,7 +483,7 @@ __global__ __launch_bounds__(512, 1) void wgrad2_kernel(const float* __restrict_
     // that iteration — a whole sub-chunk (16 MFMA steps, ~7 us) to arrive — from where iteration k + 1 stages it. With one register
     // set (request at the top of the iteration that stages the rows from its 8th step on) the launch ran 1.6x slower on operands
     // that come from HBM than on operands the producing GEMM left in the Infinity Cache: it was waiting for its rows.
-    g32x4 sa[SA], sb[SB], na[SA], nb[SB];
+    f32x4 sa[SA], sb[SB], na[SA], nb[SB];
     int va = 0, vb = 0, nva = 0, nvb = 0;
     auto fetch = [&](int rs0) {
         nva = 0; nvb = 0;
@@ -519,14 +492,14 @@ __global__ __launch_bounds__(512, 1) void wgrad2_kernel(const float* __restrict_
             const int row = rs0 + ra + i * RSA;
             const int rc = row < r_end ? row : r_end - 1;
             if (row < r_end) nva |= 1 << i;
-            na[i] = g_load4(rz, (rc * ldz + o0 + 4 * qa) * 4, 0);
+            na[i] = weight_load(rz, (rc * ldz + o0 + 4 * qa) * 4, 0);
         }
 #pragma unroll
         for (int i = 0; i < SB; ++i) {
             const int row = rs0 + rb + i * RSB;
             const int rc = row < r_end ? row : r_end - 1;
             if (row < r_end) nvb |= 1 << i;
-            nb[i] = g_load4(rxx, (rc * ldx + i0 + 4 * qb) * 4, 0);
+            nb[i] = weight_load(rxx, (rc * ldx + i0 + 4 * qb) * 4, 0);
         }
     };
     auto hand_over = [&]() {
@@ -539,18 +512,18 @@ __global__ __launch_bounds__(512, 1) void wgrad2_kernel(const float* __restrict_
     // staging piece i < SA + SB of the fetched sub-chunk: one float4 of dZ (i < SA) or of X (deferred activation applied)
     auto stage_piece = [&](int buf, int i) {
         if (i < SA) {
-            g32x4 v = sa[i];
-            if (!((va >> i) & 1)) v = g32x4{0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<g32x4*>(As + buf * (RS * LDA) + (ra + i * RSA) * LDA + 4 * qa) = v;
+            f32x4 v = sa[i];
+            if (!((va >> i) & 1)) v = f32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(As + buf * (RS * LDA) + (ra + i * RSA) * LDA + 4 * qa) = v;
         } else {
             const int k2 = i - SA;
-            g32x4 v = sb[k2];
+            f32x4 v = sb[k2];
             if (xa) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = fmaxf(__builtin_fmaf(v[k], ta[k], tb[k]), 0.f);
             }
-            if (!((vb >> k2) & 1)) v = g32x4{0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<g32x4*>(Bs + buf * (RS * LDB) + (rb + k2 * RSB) * LDB + 4 * qb) = v;
+            if (!((vb >> k2) & 1)) v = f32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(Bs + buf * (RS * LDB) + (rb + k2 * RSB) * LDB + 4 * qb) = v;
         }
     };
     constexpr int NP = SA + SB;                                 // pieces per sub-chunk (4 .. 8), one behind each of the last j-steps
@@ -592,7 +565,7 @@ __global__ __launch_bounds__(512, 1) void wgrad2_kernel(const float* __restrict_
             __builtin_amdgcn_sched_barrier(0);
         }
         if (!(EXP & 2)) hand_over();
-        if (!(EXP & 4)) g_lds_barrier();
+        if (!(EXP & 4)) lds_barrier();
         buf ^= 1;
     }
     // C/D layout: column (input channel) = lane & 31, row (output channel) = (reg & 3) + 8 (reg >> 2) + 4 half
@@ -604,7 +577,7 @@ __global__ __launch_bounds__(512, 1) void wgrad2_kernel(const float* __restrict_
             const int ci = i0 + wk * (32 * TK) + b * 32 + col;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = o0 + wn * (32 * TN) + a * 32 + g_tile_row(r, half);
+                const int co = o0 + wn * (32 * TN) + a * 32 + tile_row(r, half);
                 if (!(EXP & 16) || r == 15) P[(size_t)co * Cin + ci] = acc[a][b][r];
             }
         }
@@ -889,11 +862,7 @@ static int rows_gemm_launch(const float* X, int rows, int K, int ldx, const floa
         const int x = atoi(e);
         if (g.WR == 1 && g.RT == 2 && g.CT == 2 && g.KC == 128 && x && !in_scale) {
 #define PTT_RG_EXP_CASE(X)                                                                                              \
-            if (x == X) {                                                                                               \
-                if ((rc = set_lds_limit(reinterpret_cast<const void*>(rows_gemm_kernel<1, 2, 2, 128, false, false, X>), lds))) return rc; \
-                hipLaunchKernelGGL((rows_gemm_kernel<1, 2, 2, 128, false, false, X>), grid, dim3(256), lds, s, p);      \
-                return check_launch("rows_gemm_kernel(exp)");                                                           \
-            }
+            if (x == X) return launch("rows_gemm_kernel(exp)", rows_gemm_kernel<1, 2, 2, 128, false, false, X>, grid, dim3(256), lds, s, p);
             PTT_RG_EXP_CASE(1) PTT_RG_EXP_CASE(2) PTT_RG_EXP_CASE(3) PTT_RG_EXP_CASE(4) PTT_RG_EXP_CASE(7) PTT_RG_EXP_CASE(8) PTT_RG_EXP_CASE(15)
 #undef PTT_RG_EXP_CASE
         }
@@ -1020,12 +989,9 @@ static int linear_wgrad2_run(const float* dZ, int ldz, const float* X, int ldx, 
     if (const char* e = getenv("PTT_WG2_EXP")) {
         const int x = atoi(e);
 #define PTT_WG2_EXP_CASE(X)                                                                                             \
-        if (x == X && g.TN == 4 && g.TK == 2) {                                                                         \
-            if ((rc = set_lds_limit(reinterpret_cast<const void*>(wgrad2_kernel<4, 2, X>), lds))) return rc;            \
-            hipLaunchKernelGGL((wgrad2_kernel<4, 2, X>), grid, dim3(512), lds, s, dZ, ldz, X_, ldx, R, Cout, Cin, g.nbk, g.chunk_rows, \
-                               static_cast<float*>(ws), x_scale, x_shift);                                              \
-            return check_launch("wgrad2_kernel(exp)");                                                                  \
-        }
+        if (x == X && g.TN == 4 && g.TK == 2)                                                                           \
+            return launch("wgrad2_kernel(exp)", wgrad2_kernel<4, 2, X>, grid, dim3(512), lds, s, dZ, ldz, X_, ldx, R, Cout, Cin, g.nbk,  \
+                          g.chunk_rows, static_cast<float*>(ws), x_scale, x_shift);
         const float* X_ = X;
         PTT_WG2_EXP_CASE(1) PTT_WG2_EXP_CASE(2) PTT_WG2_EXP_CASE(3) PTT_WG2_EXP_CASE(4) PTT_WG2_EXP_CASE(7) PTT_WG2_EXP_CASE(8)
         PTT_WG2_EXP_CASE(15) PTT_WG2_EXP_CASE(16) PTT_WG2_EXP_CASE(31)

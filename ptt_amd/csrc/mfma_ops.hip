@@ -38,7 +38,7 @@
 #endif
 // GEMM loop flavours (gemm_core's PF): 0 = two register sets pinned with sched_barrier (best for the SA
 // chains and the linear kernel, measured), 1 = one-block prefetch scheduled by hipcc (best for the pair
-// kernel), 2 = two blocks in flight (slower everywhere: the L2->CU path saturates).
+// kernel).
 
 namespace ptt {
 
@@ -65,28 +65,9 @@ __device__ __forceinline__ void stagger_second_slot(int first_wave_blocks, int q
     }
 }
 
-// XCD-aware workgroup numbering (speed only, never correctness). The dispatcher is observed to place block b
-// on XCD b % 8, and each XCD has its own 4 MiB L2: with the plain numbering the workgroups of one frame are dealt
-// round-robin over all 8 XCDs, so every XCD pulls every frame's feature / q|k|v rows through its own L2. Renumbered,
-// the blocks an XCD receives are CONSECUTIVE logical workgroups = whole frames, whose rows (each used by ~16
-// neighbourhoods) hit in that XCD's L2. Measured on the pair kernel (profiles/README.md): fabric traffic per
-// launch 443 -> 88 MB (55 MB compulsory), L2 hit rate 95.6 -> 99.1 %, kernel time -2 %.
-// -DPTT_XCD_REMAP=0 restores the plain numbering.
 #ifndef PTT_LINEAR_PF
 #define PTT_LINEAR_PF 0      // the hand-pinned two-register-set K loop: 5 % faster than the rotating prefetch on the linear
 #endif                      // kernel's short launches (0.272 -> 0.259 ms per step; the pair kernel prefers form 1)
-#ifndef PTT_XCD_REMAP
-#define PTT_XCD_REMAP 1
-#endif
-__device__ __forceinline__ int logical_block() {
-#if PTT_XCD_REMAP
-    const int bid = blockIdx.x, per = (int)gridDim.x >> 3;
-    if (bid >= (per << 3)) return bid;              // the last grid % 8 blocks keep their number
-    return (bid & 7) * per + (bid >> 3);
-#else
-    return blockIdx.x;
-#endif
-}
 
 // ------------------------------------------------------------------------------------------
 // weight packing
@@ -130,14 +111,6 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const ptt_pack_job* _
 }
 
 // One K-block: 4 * RT * CT MFMAs on the first CT column tiles of acc (ACT >= CT columns wide).
-// Weight fragments are fetched with raw buffer loads: address = descriptor base (SGPRs) + per-lane byte offset (one
-// VGPR, constant for the whole GEMM) + wave-uniform byte offset (SGPR, advanced by the scalar unit). The flat
-// global_load form made hipcc recompute a 64-bit VGPR address per fragment (v_add_co / v_addc pairs): ~10 vector-ALU
-// instructions per K-block that steal issue time from the fp32 MFMAs sharing the SIMD (DESIGN.md lesson 8).
-// -DPTT_BUFFER_WEIGHTS=0 restores the flat loads.
-#ifndef PTT_BUFFER_WEIGHTS
-#define PTT_BUFFER_WEIGHTS 1
-#endif
 template <int RT, int CT, int ACT>
 __device__ __forceinline__ void gemm_mfma_block(const f32x4 (&a)[RT], const f32x4 (&b)[CT], f32x16 (&acc)[RT][ACT]) {
 #pragma unroll
@@ -161,21 +134,15 @@ __device__ __forceinline__ void gemm_mfma_block(const f32x4 (&a)[RT], const f32x
 template <int RT, int CT, int ACT, int CTS = 4, int PF = 1>   // CTS: distance (in column tiles) between this wave's tiles
 __device__ __forceinline__ void gemm_core(const float* Xs, int ldk, int nkb, const f32x4* __restrict__ Wp, int NT,
                                           int ct0, int lane, f32x16 (&acc)[RT][ACT], const f32x4* pre = nullptr) {
-    // `pre` (PF 0 and 1): the first K-block's CT weight fragments, already requested by the caller — issued
+    // `pre`: the first K-block's CT weight fragments, already requested by the caller — issued
     // before the previous layer's epilogue and barriers so that a layer does not start with an exposed L2 round trip
     static_assert(CT <= ACT, "accumulator array too narrow");
     const int row = lane & 31, half = lane >> 5;
     const float* arow = Xs + row * ldk + 4 * half;
-    const f32x4* bp = Wp + (size_t)ct0 * 64 + lane;
-    const size_t bstep = (size_t)NT * 64;
-#if PTT_BUFFER_WEIGHTS
-    const __amdgpu_buffer_rsrc_t wr = weight_rsrc(Wp);
+    const __amdgpu_buffer_rsrc_t wr = weight_rsrc(Wp);      // weight fragments come through raw buffer loads (mfma_common.h)
     const int wvoff = (ct0 * 64 + lane) * 16;             // this lane's byte offset inside a K-block row of fragments
     const int wkstep = NT * 1024;                          // bytes per K-block
 #define PTT_WFRAG(KB, U) weight_load(wr, wvoff, (KB) * wkstep + (U) * CTS * 1024)
-#else
-#define PTT_WFRAG(KB, U) (bp[(size_t)(KB) * bstep + (size_t)(U) * CTS * 64])
-#endif
 
     if constexpr (PF == 0) {                     // two register sets, order pinned with sched_barrier
         f32x4 a0[RT], a1[RT], b0[CT], b1[CT];
@@ -215,7 +182,7 @@ __device__ __forceinline__ void gemm_core(const float* Xs, int ldk, int nkb, con
             gemm_mfma_block<RT, CT, ACT>(a0, b0, acc);
         }
 #undef PTT_LOAD_BLOCK
-    } else if constexpr (PF == 1) {
+    } else {
         f32x4 bcur[CT], bnxt[CT];
 #pragma unroll
         for (int u = 0; u < CT; ++u) { bcur[u] = pre ? pre[u] : PTT_WFRAG(0, u); bnxt[u] = bcur[u]; }
@@ -237,44 +204,6 @@ __device__ __forceinline__ void gemm_core(const float* Xs, int ldk, int nkb, con
             for (int rt = 0; rt < RT; ++rt) a[rt] = *reinterpret_cast<const f32x4*>(arow + rt * 32 * ldk + (nkb - 1) * 8);
             gemm_mfma_block<RT, CT, ACT>(a, bcur, acc);
         }
-    } else {                                     // two K-blocks of weights in flight (needs nkb % 3 == 1 handling below)
-        f32x4 b0[CT], b1[CT], b2[CT];
-#pragma unroll
-        for (int u = 0; u < CT; ++u) {
-            b0[u] = bp[(size_t)u * CTS * 64];
-            b1[u] = (nkb > 1) ? bp[bstep + (size_t)u * CTS * 64] : b0[u];
-            b2[u] = b0[u];
-        }
-        int kb = 0;
-        for (; kb + 3 <= nkb; kb += 3) {
-#define PTT_STAGE(CUR, FILL, OFF)                                                                         \
-            {                                                                                             \
-                if (kb + (OFF) + 2 < nkb) {                                                               \
-                    const f32x4* bn = bp + (size_t)(kb + (OFF) + 2) * bstep;                              \
-                    _Pragma("unroll") for (int u = 0; u < CT; ++u) FILL[u] = bn[(size_t)u * CTS * 64];    \
-                }                                                                                         \
-                f32x4 a[RT];                                                                              \
-                _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                         \
-                    a[rt] = *reinterpret_cast<const f32x4*>(arow + rt * 32 * ldk + (kb + (OFF)) * 8);     \
-                gemm_mfma_block<RT, CT, ACT>(a, CUR, acc);                                                \
-            }
-            PTT_STAGE(b0, b2, 0)
-            PTT_STAGE(b1, b0, 1)
-            PTT_STAGE(b2, b1, 2)
-        }
-        // tail (nkb % 3): blocks kb, kb+1 are already in b0, b1
-        if (kb < nkb) {
-            f32x4 a[RT];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) a[rt] = *reinterpret_cast<const f32x4*>(arow + rt * 32 * ldk + kb * 8);
-            gemm_mfma_block<RT, CT, ACT>(a, b0, acc);
-            if (kb + 1 < nkb) {
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) a[rt] = *reinterpret_cast<const f32x4*>(arow + rt * 32 * ldk + (kb + 1) * 8);
-                gemm_mfma_block<RT, CT, ACT>(a, b1, acc);
-            }
-        }
-#undef PTT_STAGE
     }
 #undef PTT_WFRAG
 }
@@ -293,14 +222,6 @@ __device__ __forceinline__ void gemm_tiles(const float* Xs, int ldk, int nkb, co
             else if (nvalid == 3) gemm_core<RT, 3, CT, 4, PFM>(Xs, ldk, nkb, Wp, NT, ct0, lane, acc, pre);
         }
     }
-}
-
-// Workgroup barrier that orders LDS traffic only: unlike __syncthreads() it does not wait for outstanding
-// global loads (vmcnt), so weight fragments requested for the NEXT layer stay in flight across it.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 // First K-block of a GEMM's weights for this wave's CT column tiles w, w+4, ... (all exist).
@@ -536,6 +457,34 @@ __global__ __launch_bounds__(512, 1) void linear_small_kernel(LinearParams p) {
 // Fused set-abstraction level. A workgroup owns 64 grouped rows = 64/NS centres.
 // ------------------------------------------------------------------------------------------
 struct SaLayerDev { const float* Wp; const float* scale; const float* shift; int Cin, Cout, relu, nkb, NT; };
+
+// Host: the ABI's ptt_sa_layer array -> the table a chained kernel walks. Per layer, in this order: Cin must continue the chain
+// (PTT_EINVAL), Cout must fit the kernel's column tiles (PTT_EUNSUPPORTED), the packed weights must be there (PTT_EINVAL).
+// `cin` comes in as the width of the chain's input and leaves as the last layer's Cout; `maxk` comes in as the narrowest
+// admissible LDS tile and leaves widened to every layer's input K-blocks and every inner layer's output column tiles.
+struct LayerRules {
+    bool mult32;              // Cout must be a multiple of 32 (otherwise the last column tile is padded)
+    int cap_inner, cap_last;  // the widest inner / last layer
+    const char* cout_text;    // what the message says after "layer %d Cout=%d"
+};
+static int build_layer_table(const char* who, const ptt_sa_layer* layers, int n_layers, const LayerRules& rules, SaLayerDev* out,
+                             int& cin, int& maxk) {
+    for (int l = 0; l < n_layers; ++l) {
+        const ptt_sa_layer& s = layers[l];
+        const bool last = l == n_layers - 1;
+        if (s.Cin != cin) return fail(PTT_EINVAL, "%s: layer %d Cin=%d, expected %d", who, l, s.Cin, cin);
+        if (s.Cout <= 0 || (rules.mult32 && (s.Cout % 32) != 0) || s.Cout > (last ? rules.cap_last : rules.cap_inner))
+            return fail(PTT_EUNSUPPORTED, "%s: layer %d Cout=%d%s", who, l, s.Cout, rules.cout_text);
+        if (!s.Wpacked) return fail(PTT_EINVAL, "%s: layer %d has no weights", who, l);
+        SaLayerDev& L = out[l];
+        L.Wp = s.Wpacked; L.scale = s.scale; L.shift = s.shift; L.Cin = s.Cin; L.Cout = s.Cout; L.relu = s.relu;
+        L.nkb = (s.Cin + 7) / 8; L.NT = (s.Cout + 31) / 32;
+        if (L.nkb * 8 > maxk) maxk = L.nkb * 8;
+        if (!last && L.NT * 32 > maxk) maxk = L.NT * 32;      // an inner layer writes whole (zero-padded) column tiles
+        cin = s.Cout;
+    }
+    return PTT_OK;
+}
 struct SaParams {
     const float* xyz; const float* new_xyz; const int32_t* idx; const float* feat; float* out;
     long long fsb, fsc, fsn, osb, osc, osm;
@@ -946,12 +895,6 @@ __device__ __forceinline__ float sas_pool(const f32x16& a, float sh, int relu) {
     return relu ? fmaxf(mx, 0.f) : mx;
 }
 
-#ifndef PTT_SAS_INTERLEAVE
-#define PTT_SAS_INTERLEAVE 0    // 1: one gather instruction behind each MFMA (measured 3.5 % SLOWER than the block behind the last MFMA)
-#endif
-#ifndef PTT_SAS_EXP
-#define PTT_SAS_EXP 0    // timing experiments only (wrong results): 1 no barriers, 2 no gather, 4 no h1 writes, 8 no pool, 16 no meta
-#endif
 template <int NS>
 __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
     static_assert(NS == 32, "one centre per 32-row tile");
@@ -1062,7 +1005,7 @@ __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
         const bool more = it + 1 < ntiles;                               // last tile: re-gathers itself (branch-free loop)
         SasCentre own_next = own;
         if (more) own_next.advance(2, M);
-        if (!(PTT_SAS_EXP & 1)) lds_barrier();                           // A: P is complete; every wave is done with Q
+        lds_barrier();                                                   // A: P is complete; every wave is done with Q
         const int nn = meta_index(own_next);                             // index load in flight under the first K-blocks
         MetaXyz mx;
 
@@ -1084,7 +1027,7 @@ __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
             for (int i = 0; i < 8; ++i) {
                 if (i < 7) { bn[0] = weight_load(wr1, wvoff, (2 * i + 2) * WK1); bn[1] = weight_load(wr1, wvoff, (2 * i + 3) * WK1); }
                 SAS_A1(a1, 2 * i + 1)
-                if (i == 4 && !(PTT_SAS_EXP & 16)) mx = meta_fetch(own_next, nn);
+                if (i == 4) mx = meta_fetch(own_next, nn);
                 __builtin_amdgcn_sched_barrier(0);
                 if (i == 0) {
 #pragma unroll
@@ -1110,8 +1053,8 @@ __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
                     for (int rt = 0; rt < 2; ++rt)
                         acc1[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[rt][j], bc[1][j], acc1[rt], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (i < 4 && !(PTT_SAS_EXP & 8)) pv[i >> 1][i & 1] = sas_pool(acc[i >> 1][i & 1], (i & 1) ? sh2b : sh2a, L2.relu);
-                if (i == 6 && !(PTT_SAS_EXP & 16)) meta_store(mx);
+                if (i < 4) pv[i >> 1][i & 1] = sas_pool(acc[i >> 1][i & 1], (i & 1) ? sh2b : sh2a, L2.relu);
+                if (i == 6) meta_store(mx);
                 __builtin_amdgcn_sched_barrier(0);
                 bc[0] = bn[0]; bc[1] = bn[1];
             }
@@ -1126,10 +1069,10 @@ __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-            for (int r = (PTT_SAS_EXP & 4) ? 15 : 0; r < 16; ++r)
+            for (int r = 0; r < 16; ++r)
                 Q[(rt * 32 + tile_row(r, half)) * SAS_LDK + w * 32 + col] = fmaxf(acc1[rt][r], 0.f);
         if (it > 0) store_pooled(prev);
-        if (!(PTT_SAS_EXP & 1)) lds_barrier();                           // C: h1 is complete; every wave is done with P
+        lds_barrier();                                                   // C: h1 is complete; every wave is done with P
 
         // ---- layer 2: 128 -> 256 (column tiles w, w+4), with the gather of the next tile inside the MFMA stream ----
         {
@@ -1159,8 +1102,7 @@ __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
                     pre1[1] = weight_load(wr1, wvoff, WK1);
                 }
                 SAS_A2(a1, 2 * i + 1)
-                f32x4 v = wx0;
-                if (!(PTT_SAS_EXP & 2)) v = weight_load(rf, __builtin_bit_cast(int, mc[0]) + q * 16, 0);
+                const f32x4 v = weight_load(rf, __builtin_bit_cast(int, mc[0]) + q * 16, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (i == 0) {
 #pragma unroll
@@ -1185,16 +1127,9 @@ __global__ __launch_bounds__(256, 2) void sa_stream_kernel(SaParams p) {
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 gemm_mfma_block<2, 2, 2>(a1, bc[1], acc);
-                if (!(PTT_SAS_EXP & 2)) sas_pair_store(P, w, i, sub, q, v, mc, wx0, wx1, wx2, floor0);
-#if PTT_SAS_INTERLEAVE
-                // one gather instruction behind each MFMA instead of a block of 17 behind the last one
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // VALU
-                }
-                __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);       // the ds_write of the row pair
-#endif
+                sas_pair_store(P, w, i, sub, q, v, mc, wx0, wx1, wx2, floor0);
+                // (one gather instruction behind each MFMA, by sched_group_barrier, was measured 3.5 % slower than this block
+                //  of 17 behind the last one)
                 __builtin_amdgcn_sched_barrier(0);
                 mc = mn;
 #pragma unroll
@@ -2292,9 +2227,7 @@ static int linear_launch(const float* X, int rows, int K, int ldx, const float* 
     if (dev_switches().linear_small && vec && batch == 1 && !in_a && rows <= 8192 && K <= 520 && K >= 32) {
         const int hb = ((p.nkb + 1) / 2 + LS_PD - 1) / LS_PD * LS_PD;
         const int lds = (32 * (2 * hb * 8 + 4) + 4 * 16 * 64) * (int)sizeof(float);
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(linear_small_kernel), lds)) return rc;
-        hipLaunchKernelGGL(linear_small_kernel, dim3((rows + 31) / 32, (p.NT + 3) / 4), dim3(512), lds, s, p);
-        return check_launch("linear_small_kernel");
+        return launch("linear_small_kernel", linear_small_kernel, dim3((rows + 31) / 32, (p.NT + 3) / 4), dim3(512), lds, s, p);
     }
     const int rt64 = (rows + 63) / 64, rt32 = (rows + 31) / 32, cg256 = (p.NT + 7) / 8, cg128 = (p.NT + 3) / 4;
     int RT = dev_switches().linear_rt, CT = dev_switches().linear_ct;
@@ -2304,18 +2237,15 @@ static int linear_launch(const float* X, int rows, int K, int ldx, const float* 
     if (rows >= 32768 && Cout >= 256 && RT == 1 && CT == 1) CT = 2;
     const int lds = 2 * (RT * 32) * LIN_LDK * (int)sizeof(float);
     const dim3 grid(RT == 2 ? rt64 : rt32, CT == 2 ? cg256 : cg128, batch);
-    int rc = PTT_OK;
-#define PTT_LIN_CASE(R, V, C)                                                                                  \
-    if (RT == R && vec == V && CT == C) {                                                                      \
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(linear_kernel<R, V, C>), lds))) return rc;       \
-        hipLaunchKernelGGL((linear_kernel<R, V, C>), grid, dim3(256), lds, s, p);                              \
-    }
-    PTT_LIN_CASE(1, true, 1) PTT_LIN_CASE(1, true, 2) PTT_LIN_CASE(1, false, 1) PTT_LIN_CASE(1, false, 2)
+    auto run = [&](void (*kernel)(LinearParams)) { return launch("linear_kernel", kernel, grid, dim3(256), lds, s, p); };
 #ifdef PTT_DEV      // 64-row tiles are a sweep option only (PTT_LINEAR_TILE=21|22): the 64 x 256 one spills 80 bytes per lane
-    PTT_LIN_CASE(2, true, 1) PTT_LIN_CASE(2, true, 2) PTT_LIN_CASE(2, false, 1) PTT_LIN_CASE(2, false, 2)
+    if (RT == 2) {
+        if (vec) return run(CT == 2 ? linear_kernel<2, true, 2> : linear_kernel<2, true, 1>);
+        return run(CT == 2 ? linear_kernel<2, false, 2> : linear_kernel<2, false, 1>);
+    }
 #endif
-#undef PTT_LIN_CASE
-    return check_launch("linear_kernel");
+    if (vec) return run(CT == 2 ? linear_kernel<1, true, 2> : linear_kernel<1, true, 1>);
+    return run(CT == 2 ? linear_kernel<1, false, 2> : linear_kernel<1, false, 1>);
 }
 
 extern "C" int ptt_rows_mlp_f32(const float* X, int rows, int K, int ldx, const ptt_sa_layer* layers, int n_layers,
@@ -2329,33 +2259,35 @@ extern "C" int ptt_rows_mlp_f32(const float* X, int rows, int K, int ldx, const 
     p.X = X; p.residual = residual; p.out = out; p.rows = rows; p.K0 = K; p.ldx = ldx; p.ldr = ldr; p.ldo = ldo;
     p.n_layers = n_layers;
     int maxk = 0, cin = K;
-    for (int l = 0; l < n_layers; ++l) {
-        const ptt_sa_layer& s = layers[l];
-        const bool last = l == n_layers - 1;
-        if (s.Cin != cin) return fail(PTT_EINVAL, "ptt_rows_mlp_f32: layer %d Cin=%d, expected %d", l, s.Cin, cin);
-        if (s.Cout <= 0 || s.Cout > (last ? 384 : 256))
-            return fail(PTT_EUNSUPPORTED, "ptt_rows_mlp_f32: layer %d Cout=%d (inner layers <= 256, the last <= 384)", l, s.Cout);
-        if (!s.Wpacked) return fail(PTT_EINVAL, "ptt_rows_mlp_f32: layer %d has no weights", l);
-        SaLayerDev& L = p.L[l];
-        L.Wp = s.Wpacked; L.scale = s.scale; L.shift = s.shift; L.Cin = s.Cin; L.Cout = s.Cout; L.relu = s.relu;
-        L.nkb = (s.Cin + 7) / 8; L.NT = (s.Cout + 31) / 32;
-        if (L.nkb * 8 > maxk) maxk = L.nkb * 8;
-        if (!last && L.NT * 32 > maxk) maxk = L.NT * 32;      // an inner layer writes whole (zero-padded) column tiles
-        cin = s.Cout;
-    }
+    if (int rc = build_layer_table("ptt_rows_mlp_f32", layers, n_layers, {false, 256, 384, " (inner layers <= 256, the last <= 384)"},
+                                   p.L, cin, maxk))
+        return rc;
     if (ldo < cin || (residual && ldr < cin)) return fail(PTT_EINVAL, "ptt_rows_mlp_f32: ldo=%d ldr=%d Cout=%d", ldo, ldr, cin);
     p.ldk = maxk + 4;
     p.vec_in = ((K & 3) == 0 && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0) ? 1 : 0;
     const int lds = 32 * p.ldk * (int)sizeof(float);
-    int rc = set_lds_limit(reinterpret_cast<const void*>(rows_mlp_kernel), lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(rows_mlp_kernel, dim3((rows + 31) / 32), dim3(256), lds, as_stream(stream), p);
-    return check_launch("rows_mlp_kernel");
+    return launch("rows_mlp_kernel", rows_mlp_kernel, dim3((rows + 31) / 32), dim3(256), lds, as_stream(stream), p);
 }
 
 extern "C" size_t ptt_sa_compact_workspace(int B, int M) {
     const long long T = (long long)(B > 0 ? B : 0) * (M > 0 ? M : 0);
     return SacTable::words((size_t)T) * sizeof(int32_t);
+}
+
+// The ball table of a compacted level (ptt_sa_desc.compact_ws) into p.cws: workspace check, class counters to zero, then one
+// half-wave per ball. XYZ: distinct = first occurrence of a coordinate bit pattern (SA0), otherwise = real hit.
+template <bool XYZ>
+static int launch_ball_table(const ptt_sa_desc* d, SaParams& p, hipStream_t s) {
+    if (d->compact_ws_bytes < ptt_sa_compact_workspace(d->B, d->M) || (reinterpret_cast<uintptr_t>(d->compact_ws) & 15))
+        return fail(PTT_EWORKSPACE, "ptt_sa_fused_fwd_f32: compact_ws needs %zu bytes, 16-byte aligned (got %zu)",
+                    ptt_sa_compact_workspace(d->B, d->M), d->compact_ws_bytes);
+    const int total_centres = d->B * d->M;
+    p.cws = static_cast<int32_t*>(d->compact_ws);
+    hipLaunchKernelGGL(sa_compact_zero_kernel, dim3(1), dim3(64), 0, s, p.cws);
+    if (int rc = check_launch("sa_compact_zero_kernel")) return rc;
+    hipLaunchKernelGGL(sa_compact_kernel<XYZ>, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
+                       SacTable{p.cws, total_centres});
+    return check_launch("sa_compact_kernel");
 }
 
 extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
@@ -2394,21 +2326,10 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
         p.feat = d->l0_point_term; p.C = d->l0_channels; p.K0 = p.C;
         p.fsc = 1; p.fsn = p.C; p.fsb = (long long)d->N * p.C;
     }
-    int maxk = 0, cin = p.K0;
-    for (int l = 0; l < d->n_layers; ++l) {
-        const ptt_sa_layer& s = d->layers[l];
-        if (s.Cin != cin) return fail(PTT_EINVAL, "ptt_sa_fused_fwd_f32: layer %d Cin=%d, expected %d", l, s.Cin, cin);
-        if (s.Cout <= 0 || (s.Cout % 32) != 0 || s.Cout > 256)
-            return fail(PTT_EUNSUPPORTED, "ptt_sa_fused_fwd_f32: layer %d Cout=%d must be a multiple of 32 <= 256", l,
-                        s.Cout);
-        if (!s.Wpacked) return fail(PTT_EINVAL, "ptt_sa_fused_fwd_f32: layer %d has no weights", l);
-        SaLayerDev& L = p.L[l];
-        L.Wp = s.Wpacked; L.scale = s.scale; L.shift = s.shift; L.Cin = s.Cin; L.Cout = s.Cout; L.relu = s.relu;
-        L.nkb = (s.Cin + 7) / 8; L.NT = s.Cout / 32;
-        if (L.nkb * 8 > maxk) maxk = L.nkb * 8;
-        if (l + 1 < d->n_layers && s.Cout > maxk) maxk = s.Cout;
-        cin = s.Cout;
-    }
+    int maxk = 0, cin = p.K0, rc;
+    if ((rc = build_layer_table("ptt_sa_fused_fwd_f32", d->layers, d->n_layers, {true, 256, 256, " must be a multiple of 32 <= 256"},
+                                p.L, cin, maxk)))
+        return rc;
     {   // several kernels address these arrays with 32-bit byte offsets (buffer descriptors, scalar index arithmetic)
         const unsigned long long lim = 0x7fffffffull, B = (unsigned long long)d->B;
         if (B * d->N * 12ull >= lim || B * d->M * d->nsample * 4ull >= lim || B * d->M * (unsigned long long)cin * 4ull >= lim ||
@@ -2424,7 +2345,6 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
     p.cws = nullptr;
     const int total_centres = d->B * d->M;
     hipStream_t s = as_stream(stream);
-    int rc;
     // SA0 shape (no point features, 3 -> 64 -> 64 -> 128, 32 neighbours, BatchNorm scale folded): persistent workgroups
     // with the 50 KB of packed weights resident in LDS
     if (d->C == 0 && d->use_xyz && !hoist && d->nsample == 32 && d->n_layers == 3 && p.L[0].Cout == 64 && p.L[1].Cout == 64 &&
@@ -2444,23 +2364,11 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
             // the balls' distinct rows first (sa_compact_kernel), then the MLP on 32-row tiles of 1 - 8 balls. The tile count
             // is known on the device only: a fixed grid of at most one workgroup per CU walks it (as many tiles as balls at
             // worst), so the call stays capturable with no host synchronisation
-            if (d->compact_ws_bytes < ptt_sa_compact_workspace(d->B, d->M) || (reinterpret_cast<uintptr_t>(d->compact_ws) & 15))
-                return fail(PTT_EWORKSPACE, "ptt_sa_fused_fwd_f32: compact_ws needs %zu bytes, 16-byte aligned (got %zu)",
-                            ptt_sa_compact_workspace(d->B, d->M), d->compact_ws_bytes);
-            p.cws = static_cast<int32_t*>(d->compact_ws);
-            hipLaunchKernelGGL(sa_compact_zero_kernel, dim3(1), dim3(64), 0, s, p.cws);
-            if ((rc = check_launch("sa_compact_zero_kernel"))) return rc;
-            hipLaunchKernelGGL(sa_compact_kernel<true>, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
-                               SacTable{p.cws, total_centres});
-            if ((rc = check_launch("sa_compact_kernel"))) return rc;
+            if ((rc = launch_ball_table<true>(d, p, s))) return rc;
             if (wgs > 256 * PTT_SAL_WGS) wgs = 256 * PTT_SAL_WGS;
-            if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_lds_kernel<true>), lds))) return rc;
-            hipLaunchKernelGGL(sa_lds_kernel<true>, dim3(wgs), dim3(64 * nw), lds, s, p);
-            return check_launch("sa_lds_kernel");
+            return launch("sa_lds_kernel", sa_lds_kernel<true>, dim3(wgs), dim3(64 * nw), lds, s, p);
         }
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_lds_kernel<false>), lds))) return rc;
-        hipLaunchKernelGGL(sa_lds_kernel<false>, dim3(wgs), dim3(64 * nw), lds, s, p);
-        return check_launch("sa_lds_kernel");
+        return launch("sa_lds_kernel", sa_lds_kernel<false>, dim3(wgs), dim3(64 * nw), lds, s, p);
     }
     // small weight set (fits L1/L2 comfortably) and <= 4 column tiles everywhere: barrier-free wave-private kernel
     size_t wbytes = 0;
@@ -2477,14 +2385,7 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
         const int lds = 4 * 32 * p.ldk * (int)sizeof(float);
         const int cpw = 32 / d->nsample, per_wg = 4 * cpw;
         const dim3 grid((total_centres + per_wg - 1) / per_wg);
-        if (d->nsample == 32) {
-            if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_wave_kernel<32, 1>), lds))) return rc;
-            hipLaunchKernelGGL((sa_wave_kernel<32, 1>), grid, dim3(256), lds, s, p);
-        } else {
-            if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_wave_kernel<16, 1>), lds))) return rc;
-            hipLaunchKernelGGL((sa_wave_kernel<16, 1>), grid, dim3(256), lds, s, p);
-        }
-        return check_launch("sa_wave_kernel");
+        return launch("sa_wave_kernel", d->nsample == 32 ? sa_wave_kernel<32, 1> : sa_wave_kernel<16, 1>, grid, dim3(256), lds, s, p);
     }
     // SA1 / SA2 shape (hoisted 128-channel layer 0, then 128 -> 128 -> 256 with the BatchNorm scale folded, 32
     // neighbours): persistent double-buffered kernel that gathers the next tile inside its own MFMA stream
@@ -2498,24 +2399,12 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
         if (d->compact_ws) {
             // the balls' real hits first (sa_compact_kernel<false>), then 64-row tiles of 2 - 16 balls. As at SA0 the tile
             // count is known on the device only: a fixed grid of at most two workgroups per CU walks it
-            if (d->compact_ws_bytes < ptt_sa_compact_workspace(d->B, d->M) || (reinterpret_cast<uintptr_t>(d->compact_ws) & 15))
-                return fail(PTT_EWORKSPACE, "ptt_sa_fused_fwd_f32: compact_ws needs %zu bytes, 16-byte aligned (got %zu)",
-                            ptt_sa_compact_workspace(d->B, d->M), d->compact_ws_bytes);
-            p.cws = static_cast<int32_t*>(d->compact_ws);
-            hipLaunchKernelGGL(sa_compact_zero_kernel, dim3(1), dim3(64), 0, s, p.cws);
-            if ((rc = check_launch("sa_compact_zero_kernel"))) return rc;
-            hipLaunchKernelGGL(sa_compact_kernel<false>, dim3((total_centres + 31) / 32), dim3(256), 0, s, d->xyz, d->idx, d->N, d->M,
-                               SacTable{p.cws, total_centres});
-            if ((rc = check_launch("sa_compact_kernel"))) return rc;
+            if ((rc = launch_ball_table<false>(d, p, s))) return rc;
             const int lds = (2 * SAS_TILE + 64 * 4 + 64) * (int)sizeof(float);
-            if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_stream_compact_kernel), lds))) return rc;
-            hipLaunchKernelGGL(sa_stream_compact_kernel, dim3(p.tiles < 512 ? p.tiles : 512), dim3(256), lds, s, p);
-            return check_launch("sa_stream_compact_kernel");
+            return launch("sa_stream_compact_kernel", sa_stream_compact_kernel, dim3(p.tiles < 512 ? p.tiles : 512), dim3(256), lds, s, p);
         }
         const int lds = (2 * SAS_TILE + 4 * 16 * 4) * (int)sizeof(float);
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_stream_kernel<32>), lds))) return rc;
-        hipLaunchKernelGGL((sa_stream_kernel<32>), dim3(wgs), dim3(256), lds, s, p);
-        return check_launch("sa_stream_kernel");
+        return launch("sa_stream_kernel", sa_stream_kernel<32>, dim3(wgs), dim3(256), lds, s, p);
     }
     int RT = dev_switches().sa_rt;                       // rows per workgroup = 32 * RT (2 unless a dev build says 1)
     if (d->nsample == 64) RT = 2;                        // one centre = two row tiles
@@ -2523,14 +2412,11 @@ extern "C" int ptt_sa_fused_fwd_f32(const ptt_sa_desc* d, ptt_stream_t stream) {
     if (lds > 160 * 1024) return fail(PTT_EUNSUPPORTED, "ptt_sa_fused_fwd_f32: %d B of LDS per workgroup", lds);
     const int cpw = 32 * RT / d->nsample;
     const dim3 grid((total_centres + cpw - 1) / cpw);
-#define PTT_SA_CASE(NSV, RTV)                                                                                   \
-    if (d->nsample == NSV && RT == RTV) {                                                                       \
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(sa_fused_kernel<NSV, RTV>), lds))) return rc;     \
-        hipLaunchKernelGGL((sa_fused_kernel<NSV, RTV>), grid, dim3(256), lds, s, p);                            \
-    }
-    PTT_SA_CASE(32, 2) PTT_SA_CASE(32, 1) PTT_SA_CASE(16, 2) PTT_SA_CASE(16, 1) PTT_SA_CASE(64, 2)
-#undef PTT_SA_CASE
-    return check_launch("sa_fused_kernel");
+    void (*kernel)(SaParams) = d->nsample == 64 ? sa_fused_kernel<64, 2> : d->nsample == 32 ? sa_fused_kernel<32, 2> : sa_fused_kernel<16, 2>;
+    // 32-row workgroups: a sweep option of dev builds (PTT_SA_RT=1). They stay instantiated in a release build, where nothing
+    // selects them: without them sa_layer<32, CT, 1> is xcorr_fused_kernel<1, true>'s alone and that kernel's code changes
+    if (RT == 1) kernel = d->nsample == 32 ? sa_fused_kernel<32, 1> : sa_fused_kernel<16, 1>;
+    return launch("sa_fused_kernel", kernel, grid, dim3(256), lds, s, p);
 }
 
 extern "C" int ptt_xcorr_fused_fwd_f32(const ptt_xcorr_desc* d, ptt_stream_t stream) {
@@ -2556,19 +2442,8 @@ extern "C" int ptt_xcorr_fused_fwd_f32(const ptt_xcorr_desc* d, ptt_stream_t str
     p.out = d->out; p.osb = d->out_sb; p.osc = d->out_sc; p.osm = d->out_sn;
     p.B = d->B; p.M = d->Ns; p.n_layers = d->n_layers;
     int maxk = d->C0, cin = d->C0;
-    for (int l = 0; l < d->n_layers; ++l) {
-        const ptt_sa_layer& s = d->layers[l];
-        if (s.Cin != cin) return fail(PTT_EINVAL, "ptt_xcorr_fused_fwd_f32: layer %d Cin=%d, expected %d", l, s.Cin, cin);
-        if (s.Cout <= 0 || (s.Cout % 32) != 0 || s.Cout > 256)
-            return fail(PTT_EUNSUPPORTED, "ptt_xcorr_fused_fwd_f32: layer %d Cout=%d", l, s.Cout);
-        if (!s.Wpacked) return fail(PTT_EINVAL, "ptt_xcorr_fused_fwd_f32: layer %d has no weights", l);
-        SaLayerDev& L = p.L[l];
-        L.Wp = s.Wpacked; L.scale = s.scale; L.shift = s.shift; L.Cin = s.Cin; L.Cout = s.Cout; L.relu = s.relu;
-        L.nkb = (s.Cin + 7) / 8; L.NT = s.Cout / 32;
-        if (l + 1 < d->n_layers && s.Cout > maxk) maxk = s.Cout;
-        cin = s.Cout;
-    }
-    p.ldk = ((maxk + 7) / 8) * 8 + 4;
+    if (int rc = build_layer_table("ptt_xcorr_fused_fwd_f32", d->layers, d->n_layers, {true, 256, 256, ""}, p.L, cin, maxk)) return rc;
+    p.ldk = maxk + 4;                                    // a multiple of 8 (C0 % 8 == 0, Cout % 32 == 0) + 4
     p.first_wave = 1024; p.stagger = 2;
     if (d->split) {
         // two workgroups per search point, cosines in the kernel: see xcorr_fused_kernel<1, true>
@@ -2580,17 +2455,11 @@ extern "C" int ptt_xcorr_fused_fwd_f32(const ptt_xcorr_desc* d, ptt_stream_t str
         q.sfeat = d->search_feat; q.tfeat = d->templ_feat; q.s_sb = d->s_sb; q.s_sn = d->s_sn; q.t_sb = d->t_sb; q.t_sn = d->t_sn;
         q.C = d->C; q.eps = d->eps; q.out_sh = d->out_sh;
         const int lds = (32 * p.ldk + 32) * (int)sizeof(float);
-        int rc = set_lds_limit(reinterpret_cast<const void*>(xcorr_fused_kernel<1, true>), lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((xcorr_fused_kernel<1, true>), dim3(2 * d->B * d->Ns), dim3(256), lds, as_stream(stream), q);
-        return check_launch("xcorr_fused_kernel");
+        return launch("xcorr_fused_kernel", xcorr_fused_kernel<1, true>, dim3(2 * d->B * d->Ns), dim3(256), lds, as_stream(stream), q);
     }
     if (!d->cos_t) return fail(PTT_EINVAL, "ptt_xcorr_fused_fwd_f32: null pointer (cos_t comes from ptt_cosine_map_f32)");
     const int lds = (64 * p.ldk + 64) * (int)sizeof(float);
-    int rc = set_lds_limit(reinterpret_cast<const void*>(xcorr_fused_kernel<2, false>), lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((xcorr_fused_kernel<2, false>), dim3(d->B * d->Ns), dim3(256), lds, as_stream(stream), q);
-    return check_launch("xcorr_fused_kernel");
+    return launch("xcorr_fused_kernel", xcorr_fused_kernel<2, false>, dim3(d->B * d->Ns), dim3(256), lds, as_stream(stream), q);
 }
 
 extern "C" int ptt_cosine_map_f32(const float* search_feat, int64_t s_sb, int64_t s_sn, int64_t s_sc, const float* templ_feat,
@@ -2608,7 +2477,10 @@ extern "C" int ptt_cosine_map_f32(const float* search_feat, int64_t s_sb, int64_
 }
 
 // D x KNN instantiations of the single-head pair kernel
-#define PTT_PAIR_SHAPES(X) X(128, 8) X(128, 16) X(128, 32) X(256, 8) X(256, 16) X(256, 32) X(512, 8) X(512, 16) X(512, 32)
+template <int D>
+static void (*pair_kernel(int k))(AttnParams) {
+    return k == 8 ? pt_attn_pair_kernel<D, 8> : k == 16 ? pt_attn_pair_kernel<D, 16> : pt_attn_pair_kernel<D, 32>;
+}
 
 extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream) {
     if (!d) return fail(PTT_EINVAL, "ptt_pt_attn_pair_f32: null descriptor");
@@ -2643,23 +2515,11 @@ extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream)
     int lds = (32 * (d->D + 4) + 32 + 32 * 12) * (int)sizeof(float);
     lds += dev_switches().pair_lds_pad;                               // dev: force 1 workgroup per CU
     const dim3 grid((p.BN + pts - 1) / pts);
-    int rc = PTT_OK;
-    if (heads == 1) {
-#define PTT_PAIR_CASE(DV, KV)                                                                                        \
-        if (d->D == DV && d->k == KV) {                                                                              \
-            if ((rc = set_lds_limit(reinterpret_cast<const void*>(pt_attn_pair_kernel<DV, KV>), lds))) return rc;    \
-            hipLaunchKernelGGL((pt_attn_pair_kernel<DV, KV>), grid, dim3(256), lds, as_stream(stream), p);           \
-        }
-        PTT_PAIR_SHAPES(PTT_PAIR_CASE)
-#undef PTT_PAIR_CASE
-        return check_launch("pt_attn_pair_kernel");
-    }
-#define PTT_PAIR_HEADS(HV)                                                                                           \
-    if (heads == HV) {                                                                                               \
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(pt_attn_pair_heads_kernel<HV>), lds))) return rc;      \
-        hipLaunchKernelGGL((pt_attn_pair_heads_kernel<HV>), grid, dim3(256), lds, as_stream(stream), p);             \
-    }
-    PTT_PAIR_HEADS(2) PTT_PAIR_HEADS(4) PTT_PAIR_HEADS(8)
-#undef PTT_PAIR_HEADS
-    return check_launch("pt_attn_pair_heads_kernel");
+    hipStream_t s = as_stream(stream);
+    if (heads == 1)
+        return launch("pt_attn_pair_kernel", d->D == 128 ? pair_kernel<128>(d->k) : d->D == 256 ? pair_kernel<256>(d->k) : pair_kernel<512>(d->k),
+                      grid, dim3(256), lds, s, p);
+    return launch("pt_attn_pair_heads_kernel", heads == 2 ? pt_attn_pair_heads_kernel<2> : heads == 4 ? pt_attn_pair_heads_kernel<4>
+                                                                                                      : pt_attn_pair_heads_kernel<8>,
+                  grid, dim3(256), lds, s, p);
 }

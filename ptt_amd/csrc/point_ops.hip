@@ -532,9 +532,7 @@ __global__ __launch_bounds__(1024) void scatter_csr_count_kernel(const int32_t* 
 static int launch_scatter_csr(const int32_t* idx, int B, int N, int E, int32_t* order, int32_t* start, hipStream_t s) {
     if (N <= 2048) {
         const int lds = (16 * N + N + 1 + 16) * (int)sizeof(unsigned);
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(scatter_csr_count_kernel), lds)) return rc;
-        hipLaunchKernelGGL(scatter_csr_count_kernel, dim3(B), dim3(1024), lds, s, idx, N, E, order, start);
-        return check_launch("scatter_csr_count_kernel");
+        return launch("scatter_csr_count_kernel", scatter_csr_count_kernel, dim3(B), dim3(1024), lds, s, idx, N, E, order, start);
     }
     int Epad = 2;
     while (Epad < E) Epad <<= 1;
@@ -1367,9 +1365,7 @@ extern "C" int ptt_spatial_order_f32(const float* xyz, int B, int N, int32_t* or
     int P = 2;
     while (P < N) P <<= 1;
     const int lds = P * (int)sizeof(unsigned long long);
-    if (int rc = set_lds_limit(reinterpret_cast<const void*>(spatial_order_kernel), lds)) return rc;
-    hipLaunchKernelGGL(spatial_order_kernel, dim3(B), dim3(1024), lds, as_stream(stream), xyz, N, P, order);
-    return check_launch("spatial_order_kernel");
+    return launch("spatial_order_kernel", spatial_order_kernel, dim3(B), dim3(1024), lds, as_stream(stream), xyz, N, P, order);
 }
 
 extern "C" int ptt_fps_ws_f32(const float* xyz, int B, int N, int npoint, int32_t* idx_out, float* workspace, size_t workspace_elems,
@@ -1534,10 +1530,8 @@ static int ball_query_grid_launch(const char* who, const float* xyz, const float
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(grid_build_kernel, dim3(B), dim3(1024), 0, s, xyz, N, radius, static_cast<int32_t*>(ws));
     const int BM = B * M, lds = 4 * ((N + 31) / 32) * (int)sizeof(unsigned);
-    if (int rc = set_lds_limit(reinterpret_cast<const void*>(ball_query_grid_kernel), lds)) return rc;
-    hipLaunchKernelGGL(ball_query_grid_kernel, dim3((BM + 3) / 4), dim3(256), lds, s, xyz, centres, sel, sel_mode, BM, M, N, radius * radius,
-                       nsample, static_cast<const int32_t*>(ws), new_xyz, reinterpret_cast<long long*>(idx64), idx_out);
-    return check_launch(who);
+    return launch(who, ball_query_grid_kernel, dim3((BM + 3) / 4), dim3(256), lds, s, xyz, centres, sel, sel_mode, BM, M, N, radius * radius,
+                  nsample, static_cast<const int32_t*>(ws), new_xyz, reinterpret_cast<long long*>(idx64), idx_out);
 }
 
 extern "C" int ptt_ball_query_grid_f32(const float* new_xyz, const float* xyz, int B, int M, int N, float radius, int nsample,
@@ -1653,10 +1647,8 @@ extern "C" int ptt_scatter_add_det_f32(const float* src, const int32_t* idx, int
     if (rc) return rc;
     const int CC = 8, nchunks = (C + CC - 1) / CC;
     const size_t lds = (size_t)E * (sizeof(float) + sizeof(int));
-    if ((rc = set_lds_limit(reinterpret_cast<const void*>(scatter_add_det_kernel), (int)lds))) return rc;
-    hipLaunchKernelGGL(scatter_add_det_kernel, dim3(B * nchunks), dim3(512), lds, s, src, order, start, C, N, E, CC, nchunks,
-                       out);
-    return check_launch("scatter_add_det_kernel");
+    return launch("scatter_add_det_kernel", scatter_add_det_kernel, dim3(B * nchunks), dim3(512), (int)lds, s, src, order, start, C, N, E, CC,
+                  nchunks, out);
 }
 
 extern "C" int ptt_scatter_csr_i32(const int32_t* idx, int B, int N, int E, int32_t* order, int32_t* start, ptt_stream_t stream) {

@@ -458,14 +458,9 @@ extern "C" int ptt_row_jobs_f32(const ptt_row_job* jobs, int n_jobs, ptt_stream_
         if (P.j[i].hb & 7) pd = 4;
     }
     hipStream_t s = as_stream(stream);
-    int rc = PTT_OK;
-    bool done = false;
 #define PTT_RJ_CASE(PR, EP, PDV)                                                                                         \
-    if (!done && (pros & ~(PR)) == 0 && (epi1 & ~(EP)) == 0 && pd == (PDV)) {                                               \
-        if ((rc = set_lds_limit(reinterpret_cast<const void*>(rowjobs_kernel<PR, EP, PDV>), lds))) return rc;           \
-        hipLaunchKernelGGL((rowjobs_kernel<PR, EP, PDV>), dim3(blocks), dim3(512), lds, s, P);                          \
-        done = true;                                                                                                    \
-    }
+    if ((pros & ~(PR)) == 0 && (epi1 & ~(EP)) == 0 && pd == (PDV))                                                       \
+        return launch("rowjobs_kernel", rowjobs_kernel<PR, EP, PDV>, dim3(blocks), dim3(512), lds, s, P);
     PTT_RJ_CASE(1, 0, 4) PTT_RJ_CASE(1, 0, 8)                 // plain layers (K < 512 / K >= 512)
     PTT_RJ_CASE(3, 0, 4) PTT_RJ_CASE(3, 0, 8)                 // q|k|v beside fc_delta
     PTT_RJ_CASE(4, 0, 8)                                      // fc_gamma[0] on the pair input

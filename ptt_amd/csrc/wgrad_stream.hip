@@ -2,11 +2,9 @@
 // it is compiled with -mllvm -amdgpu-mfma-vgpr-form: with the accumulators in AGPRs the register allocator copies all of them to
 // vector registers for the final cross-wave sum and the kernel runs at one wave per SIMD (150 + 128 registers); kept in
 // vector registers throughout it is 190 registers — two waves per SIMD, which a streaming kernel needs to cover HBM latency.
-#include "common.h"
+#include "mfma_common.h"
 
 namespace ptt {
-
-typedef float f32x16t __attribute__((ext_vector_type(16)));
 
 // Weight gradient of a NARROW layer over many rows (SA0's 64 -> 64 and 64 -> 128 convolutions over 786k / 393k rows): 4 - 8
 // flops per byte read, a streaming pass over dZ and X. No LDS staging: a lane's MFMA operand IS one float of a row (channel =
@@ -22,7 +20,7 @@ __global__ __launch_bounds__(256) void wgrad_stream_kernel(const float* __restri
     extern __shared__ __attribute__((aligned(16))) float ws_red[];          // 2 x (CO * CI * 16 * 64) floats
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, half = lane >> 5, col = lane & 31;
     const int r_begin = blockIdx.x * rows_per_wg, r_end = min(R, r_begin + rows_per_wg);
-    f32x16t acc[CO][CI];
+    f32x16 acc[CO][CI];
 #pragma unroll
     for (int a = 0; a < CO; ++a)
 #pragma unroll

@@ -461,6 +461,15 @@ def linear(x, wpacked, cout, scale=None, shift=None, relu=False, residual=None, 
     return out
 
 
+def _fill_layers(dst, layers):
+    """ptt_sa_layer array `dst` <- [(wpacked, scale | None, shift | None, cin, cout, relu)]."""
+    for L, (wp, sc, sh, cin, co, relu) in zip(dst, layers):
+        L.Wpacked = wp.data_ptr()
+        L.scale = sc.data_ptr() if sc is not None else None
+        L.shift = sh.data_ptr() if sh is not None else None
+        L.Cin, L.Cout, L.relu = int(cin), int(co), int(bool(relu))
+
+
 def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, normalize_xyz=False,
                      point_major_out=True, l0=None, compact=False):
     """Fused group -> normalise -> SharedMLP(eval) -> max-pool (QueryAndGroup + SharedMLP + max_pool2d,
@@ -503,12 +512,7 @@ def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, 
     d.B, d.N, d.M, d.nsample = B, N, M, ns
     d.radius, d.use_xyz, d.normalize_xyz = float(radius), int(bool(use_xyz)), int(bool(normalize_xyz))
     d.n_layers = len(layers)
-    for i, (wp, sc, sh, cin, co, relu) in enumerate(layers):
-        L = d.layers[i]
-        L.Wpacked = wp.data_ptr()
-        L.scale = sc.data_ptr() if sc is not None else None
-        L.shift = sh.data_ptr() if sh is not None else None
-        L.Cin, L.Cout, L.relu = int(cin), int(co), int(bool(relu))
+    _fill_layers(d.layers, layers)
     if l0 is not None:
         term, wx, l0_relu = l0
         if features is not None:
@@ -565,11 +569,7 @@ def rows_mlp(x, layers, residual=None):
         _chk(res2 if res2.is_contiguous() else res2.contiguous(), "residual", torch.float32, 2)
         res2 = res2 if res2.stride(1) == 1 else res2.contiguous()
     arr = (SaLayer * len(layers))()
-    for i, (wp, sc, sh, cin, co, relu) in enumerate(layers):
-        arr[i].Wpacked = wp.data_ptr()
-        arr[i].scale = sc.data_ptr() if sc is not None else None
-        arr[i].shift = sh.data_ptr() if sh is not None else None
-        arr[i].Cin, arr[i].Cout, arr[i].relu = int(cin), int(co), int(bool(relu))
+    _fill_layers(arr, layers)
     _launch("ptt_rows_mlp_f32", x.device, _ptr(x2), rows, K, x2.stride(0), arr, len(layers), _ptr(res2), res2.stride(0) if res2 is not None else 0,
             _ptr(out), cout, timed='ptt_rows_mlp_f32')
     return out.view(*x.shape[:-1], cout)
@@ -626,12 +626,7 @@ def xcorr_fused(search_feats, templ_feats, P, w_sim, scale0, shift0, layers, eps
     d.sim_out = sim.data_ptr() if sim is not None else None
     d.B, d.Ns, d.Nt, d.C0 = B, Ns, Nt, C0
     d.n_layers = len(layers)
-    for i, (wp, sc, sh, cin, co, relu) in enumerate(layers):
-        L = d.layers[i]
-        L.Wpacked = wp.data_ptr()
-        L.scale = sc.data_ptr() if sc is not None else None
-        L.shift = sh.data_ptr() if sh is not None else None
-        L.Cin, L.Cout, L.relu = int(cin), int(co), int(bool(relu))
+    _fill_layers(d.layers, layers)
     _launch("ptt_xcorr_fused_fwd_f32", P.device, ctypes.byref(d), timed='ptt_xcorr_fused_fwd_f32')
     return out, sim
 
