@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 31
+#define PTT_ABI_VERSION 32
 
 enum {
     PTT_OK = 0,
@@ -418,8 +418,9 @@ int ptt_cosine_map_f32(const float* search_feat, int64_t s_sb, int64_t s_sn, int
  *   attn = softmax_j(a / sqrt(D));    res_i = sum_j attn * (v_j + delta)
  * replaces TransformerBlock.forward lines                  variants.py:158-163
  *   qkv (B,N,3*D) = [q | k | v] rows (from ptt_linear_f32 with the stacked weight),
- *   knn (B,N,k) i32. One head (heads 0 or 1): D 128, 256 or 512 and k 8, 16 or 32 are instantiated; several heads: D = 512
- *   and k = 16 only (PTT_EUNSUPPORTED otherwise). A 32-row tile holds 32 / k whole points of one cloud, so N % (32 / k) == 0:
+ *   knn (B,N,k) i32. One head (heads 0 or 1): D 128, 256 or 512 and k 8, 16 or 32 are instantiated; several heads (2, 4, 8 with
+ *   D / heads >= 32, one 32-column MFMA tile): D 128 or 256 and k 8, 16 or 32, D = 512 and k = 16 only — so heads 2, 4 at D 128,
+ *   heads 2, 4, 8 at D 256 and 512 (PTT_EUNSUPPORTED otherwise). A 32-row tile holds 32 / k whole points of one cloud, so N % (32 / k) == 0:
  *   at k = 8, N must be a multiple of 4; at k = 16, N must be even (a tile holds two points of
  *   one cloud; PTT_EUNSUPPORTED otherwise); at k = 32 any N. N >= k. A refused launch (PTT_EUNSUPPORTED) writes nothing.
  *   res (B,N,D); attn (B,N,k,D) or NULL (the heads discard it: centroids_voting_head.py:76).
@@ -444,7 +445,8 @@ typedef struct ptt_attn_desc {
     const int32_t* order;  /* (B,N) from ptt_spatial_order_f32, or NULL: which flat point (b*N + n) launch slot s works on. A
                               permutation inside every cloud; results do not depend on it (L2 locality of the k | v gathers) */
     int heads;             /* 0 or 1: TransformerBlock. 2, 4, 8: MulHeadTransformerLayer (multitransformer.py:11-63) with
-                              hd = D / heads: Wg1p / Wg2p are the packed hd x hd fc_gamma weights that every head shares, bg1
+                              hd = D / heads >= 32 (D 128: heads 2, 4; D 256: 2, 4, 8, any instantiated k; D 512: 2, 4, 8 at
+                              k = 16): Wg1p / Wg2p are the packed hd x hd fc_gamma weights that every head shares, bg1
                               is fc_gamma[0].bias repeated `heads` times (D floats), the softmax scale is 1 / sqrt(hd), and
                               attn is written in the reference's (B*heads, N, k, hd) layout                                  */
 } ptt_attn_desc;

@@ -1967,22 +1967,24 @@ struct AttnParams {
 
 // Multi-head form (MulHeadTransformerLayer, multitransformer.py:11-63): fc_delta is the same D x D layer; fc_gamma is ONE
 // hd x hd MLP (hd = D / HEADS) that every head shares, head h owning channels h*hd .. h*hd+hd-1. Output tile c = w + 4u
-// of a wave lies in head c / TPH (TPH = hd / 32 tiles per head) at local tile c % TPH, and reads only its head's hd input
-// channels. The wave keeps its tiles w, w+4, w+8, w+12 (the delta, gather, softmax and store code is the single-head
-// kernel's): with HEADS >= 4 the four tiles lie in four heads at the SAME local tile, so one weight fragment feeds all
-// four, each with its own A fragment; with HEADS = 2 two A and two weight fragments. 16 MFMAs per K-block either way,
-// hd / 8 K-blocks instead of D / 8.
+// (u < CT = D / 128) of a wave lies in head c / TPH (TPH = hd / 32 tiles per head) at local tile c % TPH, and reads only its
+// head's hd input channels. The wave keeps its tiles w, w+4, .. (the delta, gather, softmax and store code is the single-head
+// kernel's). With TPH <= 4 the CT tiles lie in CT heads at the SAME local tile w % TPH, so one weight fragment feeds all of
+// them, each with its own A fragment (NA = CT, NB = 1: D 512 x heads 4 / 8, D 256 x heads 2 / 4 / 8, D 128 x heads 2 / 4, where
+// CT = 1 and the one tile is simply its head's); with TPH = 8 (D 512 x heads 2) a head spans two of the wave's tiles: two A
+// and two weight fragments (NA = NB = 2). 4 CT MFMAs per K-block either way, hd / 8 K-blocks instead of D / 8.
 template <int D, int HEADS>
-__device__ __forceinline__ void gemm_heads(const float* Xs, int ldk, const float* Wp, int w, int lane, f32x16 (&acc)[1][4],
-                                           const f32x4 (&pre)[4]) {
-    static_assert(D == 512 && (HEADS == 2 || HEADS == 4 || HEADS == 8 || HEADS == 16), "4 waves x 4 column tiles of D = 512");
-    constexpr int HD = D / HEADS, TPH = HD / 32, NKB = HD / 8;
-    constexpr int NA = HEADS == 2 ? 2 : 4;      // distinct heads among the wave's tiles: A fragment of tile u = a[u / (4 / NA)]
-    constexpr int NB = HEADS == 2 ? 2 : 1;      // distinct local tiles: weight fragment of tile u = b[u % NB]
+__device__ __forceinline__ void gemm_heads(const float* Xs, int ldk, const float* Wp, int w, int lane, f32x16 (&acc)[1][D / 128],
+                                           const f32x4 (&pre)[D / 128]) {
+    static_assert(D % 128 == 0 && D % HEADS == 0 && (D / HEADS) % 32 == 0, "4 waves x D / 128 column tiles, whole 32-column tiles per head");
+    constexpr int CT = D / 128, HD = D / HEADS, TPH = HD / 32, NKB = HD / 8;
+    constexpr int NB = TPH > 4 ? TPH / 4 : 1;   // distinct local tiles among the wave's: weight fragment of tile u = b[u % NB]
+    constexpr int NA = CT / NB;                 // distinct heads: A fragment of tile u = a[u / NB]
+    static_assert(NB <= CT && NA * NB == CT && HEADS > 1, "a head holds at most the wave's CT tiles");
     const int row = lane & 31, half = lane >> 5;
     const float* arow[NA];
 #pragma unroll
-    for (int i = 0; i < NA; ++i) arow[i] = Xs + row * ldk + 4 * half + ((w + 4 * i * (4 / NA)) / TPH) * HD;
+    for (int i = 0; i < NA; ++i) arow[i] = Xs + row * ldk + 4 * half + ((w + 4 * i * NB) / TPH) * HD;
     const __amdgpu_buffer_rsrc_t wr = weight_rsrc(Wp);
     int wvoff[NB];
 #pragma unroll
@@ -1998,8 +2000,8 @@ __device__ __forceinline__ void gemm_heads(const float* Xs, int ldk, const float
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u / (4 / NA)][j], bcur[u % NB][j], acc[0][u], 0, 0, 0);
+            for (int u = 0; u < CT; ++u)
+                acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u / NB][j], bcur[u % NB][j], acc[0][u], 0, 0, 0);
     };
     // gemm_core's PF = 1 form: one block of weights in flight, the last block peeled
     for (int kb = 0; kb + 1 < NKB; ++kb) {
@@ -2014,8 +2016,8 @@ __device__ __forceinline__ void gemm_heads(const float* Xs, int ldk, const float
 
 // First K-block of a per-head fc_gamma weight for this wave's NB distinct local tiles (gemm_heads).
 template <int D, int HEADS>
-__device__ __forceinline__ void prefetch_first_block_heads(const float* Wp, int w, int lane, f32x4 (&pre)[4]) {
-    constexpr int TPH = D / HEADS / 32, NB = HEADS == 2 ? 2 : 1;
+__device__ __forceinline__ void prefetch_first_block_heads(const float* Wp, int w, int lane, f32x4 (&pre)[D / 128]) {
+    constexpr int TPH = D / HEADS / 32, NB = TPH > 4 ? TPH / 4 : 1;
     const f32x4* bp = reinterpret_cast<const f32x4*>(Wp) + lane;
 #pragma unroll
     for (int i = 0; i < NB; ++i) pre[i] = bp[(size_t)((w + 4 * i) % TPH) * 64];
@@ -2027,9 +2029,8 @@ __global__ __launch_bounds__(256, 2) void pt_attn_pair_kernel(AttnParams p) {
 #include "pt_attn_pair_body.h"
 }
 
-template <int HEADS>
+template <int D, int KNN, int HEADS>
 __global__ __launch_bounds__(256, 2) void pt_attn_pair_heads_kernel(AttnParams p) {
-    constexpr int D = 512, KNN = 16;
 #include "pt_attn_pair_body.h"
 }
 
@@ -2482,6 +2483,20 @@ static void (*pair_kernel(int k))(AttnParams) {
     return k == 8 ? pt_attn_pair_kernel<D, 8> : k == 16 ? pt_attn_pair_kernel<D, 16> : pt_attn_pair_kernel<D, 32>;
 }
 
+// D x KNN x HEADS instantiations of the multi-head pair kernel (the caller has checked the envelope: hd = D / HEADS >= 32)
+template <int D, int HEADS>
+static void (*pair_heads_kernel(int k))(AttnParams) {
+    if constexpr (D == 512) return pt_attn_pair_heads_kernel<512, 16, HEADS>;
+    else return k == 8 ? pt_attn_pair_heads_kernel<D, 8, HEADS> : k == 16 ? pt_attn_pair_heads_kernel<D, 16, HEADS>
+                                                                         : pt_attn_pair_heads_kernel<D, 32, HEADS>;
+}
+
+template <int D>
+static void (*pair_heads_kernel(int k, int heads))(AttnParams) {
+    if constexpr (D >= 256) { if (heads == 8) return pair_heads_kernel<D, 8>(k); }
+    return heads == 2 ? pair_heads_kernel<D, 2>(k) : pair_heads_kernel<D, 4>(k);
+}
+
 extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream) {
     if (!d) return fail(PTT_EINVAL, "ptt_pt_attn_pair_f32: null descriptor");
     if (d->B < 0 || d->N <= 0) return fail(PTT_EINVAL, "ptt_pt_attn_pair_f32: B=%d N=%d", d->B, d->N);
@@ -2490,9 +2505,9 @@ extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream)
         return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: D=%d k=%d (D 128, 256, 512 x k 8, 16, 32 are instantiated)", d->D, d->k);
     if (heads != 1 && heads != 2 && heads != 4 && heads != 8)
         return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d (1, 2, 4, 8 are instantiated)", d->heads);
-    if (heads > 1 && (d->D != 512 || d->k != 16))
-        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d D=%d k=%d (several heads: D=512, k=16 is instantiated)", heads,
-                    d->D, d->k);
+    if (heads > 1 && ((d->D == 512 && d->k != 16) || d->D / heads < 32))
+        return fail(PTT_EUNSUPPORTED, "ptt_pt_attn_pair_f32: heads=%d D=%d k=%d (several heads: D 128, 256 x k 8, 16, 32 and D 512 x k 16 "
+                                      "are instantiated, heads 2, 4, 8 with D / heads >= 32)", heads, d->D, d->k);
     if (d->B == 0) return PTT_OK;
     if (!d->xyz || !d->knn || !d->qkv || !d->Wd1p || !d->Wd2p || !d->bd2 || !d->Wg1p || !d->bg1 ||
         !d->Wg2p || !d->res)
@@ -2519,7 +2534,7 @@ extern "C" int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream)
     if (heads == 1)
         return launch("pt_attn_pair_kernel", d->D == 128 ? pair_kernel<128>(d->k) : d->D == 256 ? pair_kernel<256>(d->k) : pair_kernel<512>(d->k),
                       grid, dim3(256), lds, s, p);
-    return launch("pt_attn_pair_heads_kernel", heads == 2 ? pt_attn_pair_heads_kernel<2> : heads == 4 ? pt_attn_pair_heads_kernel<4>
-                                                                                                      : pt_attn_pair_heads_kernel<8>,
+    return launch("pt_attn_pair_heads_kernel", d->D == 128 ? pair_heads_kernel<128>(d->k, heads) : d->D == 256 ? pair_heads_kernel<256>(d->k, heads)
+                                                                                                     : pair_heads_kernel<512>(d->k, heads),
                   grid, dim3(256), lds, s, p);
 }

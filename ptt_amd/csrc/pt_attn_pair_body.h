@@ -1,4 +1,4 @@
-// Body of the Point-Transformer pair kernels (mfma_ops.hip: pt_attn_pair_kernel<D, KNN>, pt_attn_pair_heads_kernel<HEADS>),
+// Body of the Point-Transformer pair kernels (mfma_ops.hip: pt_attn_pair_kernel<D, KNN>, pt_attn_pair_heads_kernel<D, KNN, HEADS>),
 // included inside both kernel definitions with D, KNN, HEADS and `AttnParams p` in scope. Written out in each kernel instead of
 // called as an inlined device function: the single-head kernel then compiles to exactly the instructions it had before
 // the multi-head form existed (an inlined body is optimised before it meets the kernel's attributes and comes out

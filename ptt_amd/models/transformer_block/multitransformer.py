@@ -8,14 +8,16 @@ One layer is TransformerBlock's vector attention split into `heads` heads of hd 
 and the block runs `layers` deep copies in sequence. Parameter names (layers.{i}.fc1, fc2, fc_delta.{0,2}, fc_gamma.{0,2},
 w_qs, w_ks, w_vs, proj, norm1, norm2) are the reference's, so its checkpoints load unchanged.
 
-Eval mode on a HIP device (float32, d_model 512, k 16, an even number of points, heads 1 / 2 / 4 / 8) runs one kNN per block
-and per layer: the q|k|v projection with fc1 folded in, the attention (many points: the pair kernel's per-head form, whose
-fc_gamma GEMMs read only their head's hd input channels; one frame: the row-job chain of TransformerBlock with fc_gamma
-expanded to its block-diagonal D x D form), proj, a LayerNorm, fc2 and a LayerNorm with the residual. Return contract as
+Eval mode on a HIP device (float32; d_model 128 / 256 with k 8 / 16 / 32, d_model 512 with k 16; heads 1 / 2 / 4 / 8 with
+hd >= 32, i.e. not 8 heads at d_model 128; a number of points >= k that is a multiple of 32 // k) runs one kNN per block
+and per layer: the q|k|v projection with fc1 folded in, the attention (the pair kernel's per-head form, whose
+fc_gamma GEMMs read only their head's hd input channels; at (512, 16) one frame without attn takes the row-job chain of
+TransformerBlock with fc_gamma expanded to its block-diagonal D x D form — that chain has 512 channels and 16 neighbours built
+in, every other shape runs the pair kernel whatever B * N is), proj, a LayerNorm, fc2 and a LayerNorm with the residual. Return contract as
 TransformerBlock: `forward(xyz, features, knn=None, want_attn=True) -> (res, attn)`, attn the LAST layer's
 (B*heads, N, k, hd) tensor, or None when the caller opts out with want_attn=False.
 
-Training mode on a HIP device (train_ops.mul_block_usable: float32, d_model 512, k 16, heads 1 / 2 / 4 / 8, no dropout) runs on the
+Training mode on a HIP device (train_ops.mul_block_usable: float32, the same (d_model, k, heads) envelope, no dropout) runs on the
 row kernels of ptt_amd/train_ops.py as TransformerBlock's training step does: one kNN and one CSR order of its indices per block,
 per layer the Linears on the row GEMMs, the attention core with the heads' shared fc_gamma, and both LayerNorms on the training
 LayerNorm kernels. Everything else (CPU, other shapes, a non-zero dropout) follows the reference's ops in stock torch."""
@@ -29,7 +31,8 @@ from ...param_cache import ParamCache
 from ..model_utils import get_clones, index_points, square_distance
 from .variants import PER_LAYER_MAX_POINTS, SPATIAL_ORDER_MIN_POINTS, _rows2d
 
-FUSED_HEADS = (1, 2, 4, 8)          # the head counts ptt_pt_attn_pair_f32 instantiates (hd = 512, 256, 128, 64)
+FUSED_HEADS = (1, 2, 4, 8)          # the head counts ptt_pt_attn_pair_f32 instantiates, where hd = d_model / heads >= 32
+ROW_JOB_CHAIN = (512, 16)           # (d_model, k) of the one-frame row-job chain (rowjobs.hip: both are built in)
 
 
 class MulHeadTransformerLayer(nn.Module):
@@ -70,6 +73,10 @@ class MulHeadTransformerLayer(nn.Module):
         # the one-frame chain runs fc_gamma on the row-job kernel as its block-diagonal D x D expansion (diagonal blocks =
         # the shared hd x hd weight); the pair kernel reads the hd x hd weights themselves
         blockdiag = lambda wt: torch.block_diag(*([f(wt)] * H)).contiguous()
+        chain = {}
+        if (self.d_model, self.k) == ROW_JOB_CHAIN:
+            chain = dict(wg1_bd=ops.pack_weight(blockdiag(self.fc_gamma[0].weight)),
+                         wg2_bd=ops.pack_weight(blockdiag(self.fc_gamma[2].weight)))
         return dict(
             qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
             qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
@@ -77,12 +84,10 @@ class MulHeadTransformerLayer(nn.Module):
             wd2=ops.pack_weight(self.fc_delta[2].weight), bd2=f(self.fc_delta[2].bias),
             wg1=ops.pack_weight(self.fc_gamma[0].weight), wg2=ops.pack_weight(self.fc_gamma[2].weight),
             bg1=f(self.fc_gamma[0].bias).repeat(H).contiguous(), bg2=f(self.fc_gamma[2].bias).repeat(H).contiguous(),
-            wg1_bd=ops.pack_weight(blockdiag(self.fc_gamma[0].weight)),
-            wg2_bd=ops.pack_weight(blockdiag(self.fc_gamma[2].weight)),
             w1b=torch.cat((f(self.fc_delta[0].weight), f(self.fc_delta[0].bias)[:, None]), 1).contiguous(),
             proj=ops.pack_weight(self.proj.weight),
             fc2=ops.pack_weight(self.fc2.weight), fc2_b=f(self.fc2.bias),
-            n1w=f(self.norm1.weight), n1b=f(self.norm1.bias), n2w=f(self.norm2.weight), n2b=f(self.norm2.bias))
+            n1w=f(self.norm1.weight), n1b=f(self.norm1.bias), n2w=f(self.norm2.weight), n2b=f(self.norm2.bias), **chain)
 
     def _fused(self, xyz, features, knn_idx, rel, want_attn, order):
         """One layer on the HIP kernels; the caller has checked MulTransformerBlock._fusable and formed the kNN."""
@@ -90,7 +95,7 @@ class MulHeadTransformerLayer(nn.Module):
         D, H, k = self.d_model, self.heads, self.k
         B, N = xyz.shape[0], xyz.shape[1]
         dev = xyz.device
-        if B * N <= PER_LAYER_MAX_POINTS and not want_attn:
+        if (D, k) == ROW_JOB_CHAIN and B * N <= PER_LAYER_MAX_POINTS and not want_attn:
             # one frame: TransformerBlock's row-job chain (variants.py: the per-layer form), fc_gamma block-diagonal
             qkv = torch.empty((B, N, 3 * D), dtype=torch.float32, device=dev)
             pos = torch.empty((B * N * k, D), dtype=torch.float32, device=dev)
@@ -166,18 +171,20 @@ class MulTransformerBlock(nn.Module):
         self.d_points = d_points
 
     def _fusable(self, xyz, features):
-        """As TransformerBlock._fusable, plus the instantiated head counts."""
+        """As TransformerBlock._fusable, with the (d_model, k, heads) envelope of the multi-head pair kernel (ops.mul_block_supported)."""
         if self.training or not xyz.is_cuda:
             return False
         name = 'MulTransformerBlock(d_model=%d, k=%d, heads=%d)' % (self.d_model, self.k, self.heads)
         if ops.autograd_recording(self, xyz, features):
             return ops.note_unfused(name, 'autograd is recording (wrap inference in torch.no_grad())')
-        if self.d_model != 512 or self.k != 16:
-            return ops.note_unfused(name, 'ptt_pt_attn_pair_f32 instantiates d_model 512, k 16')
         if self.heads not in FUSED_HEADS:
             return ops.note_unfused(name, 'ptt_pt_attn_pair_f32 instantiates heads %s' % (FUSED_HEADS,))
-        if xyz.shape[1] % 2 != 0 or xyz.shape[1] < self.k:
-            return ops.note_unfused(name, 'needs an even number of points >= k (got %d)' % xyz.shape[1])
+        if not ops.mul_block_supported(self.d_model, self.k, self.heads):
+            return ops.note_unfused(name, 'MulTransformerBlock runs fused at d_model 128, 256 x k 8, 16, 32 and d_model 512 x k 16, '
+                                          'with d_model / heads >= 32')
+        if xyz.shape[1] % (32 // self.k) != 0 or xyz.shape[1] < self.k:
+            return ops.note_unfused(name, 'needs a number of points >= k that is a multiple of %d (got %d)'
+                                    % (32 // self.k, xyz.shape[1]))
         if features.dtype != torch.float32 or xyz.dtype != torch.float32:
             return ops.note_unfused(name, 'inputs must be float32')
         return True

@@ -647,14 +647,31 @@ def spatial_order(xyz):
     return order
 
 
+PAIR_ENVELOPE = ("one head: d_model 128, 256, 512 x k 8, 16, 32; heads 2, 4, 8 with d_model / heads >= 32: d_model 128, 256 x "
+                 "k 8, 16, 32 and d_model 512 x k 16")
+
+
+def pair_heads_supported(d_model, k, heads):
+    """The (d_model, k, heads) shapes ptt_pt_attn_pair_f32 instantiates (include/ptt_hip.h), PAIR_ENVELOPE in words."""
+    if d_model not in (128, 256, 512) or k not in (8, 16, 32) or heads not in (1, 2, 4, 8):
+        return False
+    return heads == 1 or (d_model // heads >= 32 and (d_model != 512 or k == 16))
+
+
+def mul_block_supported(d_model, k, heads):
+    """MulTransformerBlock's HIP envelope, eval and training: pair_heads_supported, and at d_model 512 k 16 for one head too."""
+    return pair_heads_supported(d_model, k, heads) and (d_model != 512 or k == 16)
+
+
 def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_model, want_attn=True, rel=None, order=None,
                  heads=1):
     """Fused per-(point,neighbour) part of TransformerBlock.forward (variants.py:158-163).
     wd1p = pack_delta0(fc_delta[0].weight, fc_delta[0].bias); the other weights from pack_weight. order: spatial_order(xyz) or
     None — which point every launch slot works on (the results do not depend on it).
     One head: d_model 128 / 256 / 512 and k 8 / 16 / 32 neighbours, N >= k a multiple of 32 // k (ValueError otherwise).
-    heads > 1 (2, 4, 8): MulHeadTransformerLayer's attention (multitransformer.py:46-56) — wg1p / wg2p are the packed
-    hd x hd fc_gamma weights every head shares (hd = d_model / heads), bg1 is fc_gamma[0].bias repeated `heads` times.
+    heads > 1 (2, 4, 8 with hd = d_model / heads >= 32): MulHeadTransformerLayer's attention (multitransformer.py:46-56) at d_model
+    128 / 256 with k 8 / 16 / 32 and at d_model 512 with k 16 (pair_heads_supported; ValueError otherwise) — wg1p / wg2p are the packed
+    hd x hd fc_gamma weights every head shares, bg1 is fc_gamma[0].bias repeated `heads` times.
     Returns (res (B,N,D), attn | None): attn (B,N,k,D), or (B*heads,N,k,hd) when heads > 1."""
     _chk(xyz, "xyz", torch.float32, 3)
     _chk(knn_idx, "knn_idx", torch.int32, 3)
@@ -663,9 +680,8 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
     k = knn_idx.shape[2]
     D = int(d_model)
     # what ptt_pt_attn_pair_f32 instantiates (include/ptt_hip.h): said here before anything is allocated
-    if D not in (128, 256, 512) or k not in (8, 16, 32) or (heads > 1 and (D, k) != (512, 16)):
-        raise ValueError("pt_attn_pair: d_model=%d k=%d heads=%d (one head: d_model 128, 256, 512 x k 8, 16, 32; several heads: "
-                         "d_model 512, k 16)" % (D, k, heads))
+    if not pair_heads_supported(D, k, heads):
+        raise ValueError("pt_attn_pair: d_model=%d k=%d heads=%d (%s)" % (D, k, heads, PAIR_ENVELOPE))
     if N % (32 // k) != 0 or N < k:
         raise ValueError("pt_attn_pair: N=%d must be a multiple of %d (the points of a 32-row tile) and >= k=%d" % (N, 32 // k, k))
     if tuple(knn_idx.shape[:2]) != (B, N) or tuple(qkv.shape) != (B, N, 3 * D):

@@ -994,10 +994,12 @@ MUL_BLOCK_HEADS = (1, 2, 4, 8)
 
 
 def mul_block_usable(block, xyz, features):
-    """MulTransformerBlock's training step on the row kernels: training mode, HIP device, float32, k 16, d_model 512, 1 / 2 / 4 / 8
-    heads, at most 16384 (point, neighbour) rows per cloud, no dropout after proj (a non-zero proj_drop stays on stock torch)."""
+    """MulTransformerBlock's training step on the row kernels: training mode, HIP device, float32, the (d_model, k, heads) envelope of
+    the eval path (ops.mul_block_supported: d_model 128 / 256 x k 8 / 16 / 32, d_model 512 x k 16, 1 / 2 / 4 / 8 heads of at least 32
+    channels), at most 16384 (point, neighbour) rows per cloud, no dropout after proj (a non-zero proj_drop stays on stock torch)."""
     return bool(block.training and xyz.is_cuda and features.is_cuda and features.dtype == torch.float32 and xyz.dtype == torch.float32
-                and block.k == 16 and block.d_model == 512 and block.heads in MUL_BLOCK_HEADS and xyz.shape[1] >= block.k
+                and block.heads in MUL_BLOCK_HEADS and ops.mul_block_supported(block.d_model, block.k, block.heads)
+                and xyz.shape[1] >= block.k
                 and xyz.shape[1] * block.k <= 16384 and all(layer.proj_drop.p == 0 for layer in block.layers))
 
 
