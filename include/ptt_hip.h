@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 32
+#define PTT_ABI_VERSION 33
 
 enum {
     PTT_OK = 0,
@@ -1023,6 +1023,54 @@ int ptt_adam_clip_step_f32(const ptt_adam_tensor* tensors_device, const int32_t*
 int ptt_adam_clip_step_dev_f32(const ptt_adam_tensor* tensors_device, const int32_t* chunk_tensor_device, const int64_t* chunk_first_device,
                                int n_chunks, const ptt_adam_hyper* hyper_device, int clip, double* partial, size_t partial_elems,
                                float* norm_out, ptt_stream_t stream);
+/* The same step for every optimizer of the reference's OPTIMIZATION block (tools/train_utils/optimization/__init__.py:11-39):
+ * clip_grad_norm_(ALL parameters, max_norm) + optimizer.step() over a table whose rows carry a GROUP index into an array of
+ * per-group hyper-parameters. ONE norm is formed over every row of every group (what clip_grad_norm_(model.parameters(), ..)
+ * in front of optimizer.step() computes); chunking, the float64 partial sums combined in a fixed order and
+ * clip = min(1, max_norm / (norm + 1e-6)) are those of ptt_adam_clip_step_f32. hyper[g].kind, with g' = clip g:
+ *   PTT_OPTIM_ADAM   torch.optim.Adam: g' += weight_decay p (L2), then the update of ptt_adam_clip_step_f32, bit for bit
+ *   PTT_OPTIM_ADAMW  torch.optim.AdamW (= OptimWrapper.step with true_wd, fastai_optim.py:132-149): p *= decay, decay =
+ *                    1 - lr weight_decay formed in double by the caller; then the Adam update without the L2 term
+ *   PTT_OPTIM_SGD    torch.optim.SGD, dampening 0, no nesterov: g' += weight_decay p; buf = g' when first_step != 0 and
+ *                    beta1 buf + g' otherwise (beta1 = the momentum); p += (-step_size) buf, step_size = lr. beta1 == 0: no
+ *                    buffer, state1 may be NULL and p += (-step_size) g'
+ * state1 = exp_avg | momentum_buffer, state2 = exp_avg_sq | NULL. step_size / bias2_sqrt as in ptt_adam_hyper, per group (groups
+ * may stand at different step counts). max_norm <= 0: no clipping (partial may be NULL); write_clipped: .grad *= clip in place.
+ * Refused with PTT_EINVAL, nothing launched: a null table or hyper, n_groups < 1 (more than PTT_OPTIM_MAX_GROUPS: PTT_EUNSUPPORTED), an unknown kind, an
+ * Adam kind with bias2_sqrt <= 0 or eps < 0; and, when tensors_host (optional: the host copy of the n_tensors rows the device
+ * table was uploaded from) is given, a row whose group lies outside [0, n_groups), whose param / grad is null, or an SGD row
+ * with beta1 != 0 and a null state1, an Adam row with a null state. PTT_EWORKSPACE: clipping with partial_elems < n_chunks. */
+#define PTT_OPTIM_ADAM 0
+#define PTT_OPTIM_ADAMW 1
+#define PTT_OPTIM_SGD 2
+#define PTT_OPTIM_MAX_GROUPS 8
+typedef struct ptt_optim_tensor {
+    float* param;
+    float* grad;
+    float* state1;
+    float* state2;
+    int64_t n;
+    int32_t group, reserved;
+} ptt_optim_tensor;
+typedef struct ptt_optim_hyper {
+    int32_t kind, first_step;
+    float beta1, beta2, one_minus_beta1, one_minus_beta2, eps, step_size, bias2_sqrt, weight_decay, decay;
+    int32_t reserved;
+} ptt_optim_hyper;
+int ptt_optim_clip_step_f32(const ptt_optim_tensor* tensors_device, const ptt_optim_tensor* tensors_host, int n_tensors,
+                            const int32_t* chunk_tensor_device, const int64_t* chunk_first_device, int n_chunks,
+                            const ptt_optim_hyper* hyper, int n_groups, float max_norm, int write_clipped, double* partial,
+                            size_t partial_elems, float* norm_out, ptt_stream_t stream);
+/* The same two launches with the n_groups hyper-parameter entries read from DEVICE memory when the update launch runs: the form
+ * a captured training step replays, the host writing every group's entry (a OneCycle schedule moves lr and beta1 on every step)
+ * into hyper_device before each replay. max_norm and write_clipped are launch arguments: a capture fixes them. The entries
+ * cannot be seen here, so only the table (tensors_host: group range, null param / grad), n_groups and the workspace are checked;
+ * a row the update launch finds unusable (group out of range, unknown kind, a state its kind needs is null) is left untouched.
+ * Arithmetic identical to ptt_optim_clip_step_f32. */
+int ptt_optim_clip_step_dev_f32(const ptt_optim_tensor* tensors_device, const ptt_optim_tensor* tensors_host, int n_tensors,
+                                const int32_t* chunk_tensor_device, const int64_t* chunk_first_device, int n_chunks,
+                                const ptt_optim_hyper* hyper_device, int n_groups, float max_norm, int write_clipped, double* partial,
+                                size_t partial_elems, float* norm_out, ptt_stream_t stream);
 /* The two element-wise ends of CosineSimAug's cosine map in training (p2b_xcoor.py:35-42 via nn.CosineSimilarity); the map
  * itself is a batched product of unit rows.
  *   ptt_unit_rows_f32     x addressed as x[b * sb + j * sn + c * sc] (any layout) -> unit (B,n,C) rows x / max(|x|, eps) and

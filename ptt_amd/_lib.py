@@ -79,6 +79,8 @@ PTT_SA_MAX_LAYERS = DEFINES["PTT_SA_MAX_LAYERS"]
 PTT_MAX_SEGMENTS = DEFINES["PTT_MAX_SEGMENTS"]
 PTT_CROP_JOBS_BY_VALUE_MAX = DEFINES["PTT_CROP_JOBS_BY_VALUE_MAX"]
 PTT_TRAIN_MAX_CANDS = DEFINES["PTT_TRAIN_MAX_CANDS"]
+PTT_OPTIM_MAX_GROUPS = DEFINES["PTT_OPTIM_MAX_GROUPS"]
+OPTIM_KINDS = {"adam": DEFINES["PTT_OPTIM_ADAM"], "adamw": DEFINES["PTT_OPTIM_ADAMW"], "sgd": DEFINES["PTT_OPTIM_SGD"]}
 
 
 class CropJob(Structure):
@@ -186,6 +188,19 @@ class AdamHyper(Structure):
     """ptt_adam_hyper (passed by value, host memory)."""
     _fields_ = [("beta1", c_float), ("beta2", c_float), ("one_minus_beta1", c_float), ("one_minus_beta2", c_float), ("eps", c_float), ("step_size", c_float), ("bias2_sqrt", c_float),
                 ("weight_decay", c_float), ("max_norm", c_float), ("write_clipped", c_int32)]
+
+
+class OptimTensor(Structure):
+    """ptt_optim_tensor: one parameter with its gradient, its optimizer state and its group; arrays of these are uploaded to the device."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state1", c_void_p), ("state2", c_void_p), ("n", c_int64),
+                ("group", c_int32), ("reserved", c_int32)]
+
+
+class OptimHyper(Structure):
+    """ptt_optim_hyper: one parameter group's hyper-parameters (arrays of these: host memory, or device memory in the _dev form)."""
+    _fields_ = [("kind", c_int32), ("first_step", c_int32), ("beta1", c_float), ("beta2", c_float), ("one_minus_beta1", c_float),
+                ("one_minus_beta2", c_float), ("eps", c_float), ("step_size", c_float), ("bias2_sqrt", c_float), ("weight_decay", c_float),
+                ("decay", c_float), ("reserved", c_int32)]
 
 
 class SaLayer(Structure):

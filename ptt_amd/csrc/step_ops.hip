@@ -149,13 +149,17 @@ static int loss_desc_check(const char* what, const ptt_track_loss_desc* d) {
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr int ADAM_CHUNK = 4096;        // elements per workgroup (256 threads x 16)
 
-__global__ __launch_bounds__(256) void grad_sqsum_kernel(const ptt_adam_tensor* __restrict__ tensors, const int32_t* __restrict__ tensor_of,
+// Row: ptt_adam_tensor or ptt_optim_tensor (only .grad and .n are read)
+template <typename Row>
+__global__ __launch_bounds__(256) void grad_sqsum_kernel(const Row* __restrict__ tensors, const int32_t* __restrict__ tensor_of,
                                                          const int64_t* __restrict__ first, double* __restrict__ partial) {
     __shared__ double red[4];
-    const ptt_adam_tensor t = tensors[tensor_of[blockIdx.x]];
-    const int64_t e0 = first[blockIdx.x], e1 = e0 + ADAM_CHUNK < t.n ? e0 + ADAM_CHUNK : t.n;
+    const Row& t = tensors[tensor_of[blockIdx.x]];
+    const float* __restrict__ grad = t.grad;
+    const int64_t n = t.n;
+    const int64_t e0 = first[blockIdx.x], e1 = e0 + ADAM_CHUNK < n ? e0 + ADAM_CHUNK : n;
     double s = 0.0;
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) { const double g = (double)t.grad[e]; s += g * g; }
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) { const double g = (double)grad[e]; s += g * g; }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -204,6 +208,111 @@ __global__ __launch_bounds__(256) void adam_update_kernel(const ptt_adam_tensor*
         t.param[e] = p - h.step_size * (m / denom);                                      // addcdiv_(exp_avg, denom, value=-step_size)
         if (h.write_clipped) t.grad[e] = t.grad[e] * clip;                               // leave .grad as clip_grad_norm_ would
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The same two passes for Adam, AdamW and SGD over ONE table: every row names its parameter group, the hyper-parameters are an
+// array with one entry per group, and the norm is formed over every row of every group. Each kind follows the operation order of
+// the torch function it stands for (torch/optim/adam.py, sgd.py, the multi-tensor forms):
+//   Adam   as adam_update_kernel
+//   AdamW  p *= 1 - lr wd first (the caller forms the factor in double), then Adam without the L2 term
+//   SGD    g' = clip g (+ wd p);  buf = g' (first step) | momentum buf + g';  p += (-lr) buf;  momentum == 0: no buffer
+// ------------------------------------------------------------------------------------------------------------------------------
+struct optim_groups { ptt_optim_hyper g[PTT_OPTIM_MAX_GROUPS]; };
+
+template <bool DEV>
+__global__ __launch_bounds__(256) void optim_update_kernel(const ptt_optim_tensor* __restrict__ tensors, const int32_t* __restrict__ tensor_of,
+                                                           const int64_t* __restrict__ first, const double* __restrict__ partial, int n_partial,
+                                                           optim_groups h_value, const ptt_optim_hyper* __restrict__ h_device, int n_groups,
+                                                           float max_norm, int write_clipped, float* __restrict__ norm_out) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    __shared__ float clip_s;
+    float clip = 1.f;
+    if (max_norm > 0.f) {
+        double s = 0.0;
+        for (int k = threadIdx.x; k < n_partial; k += 256) s += partial[k];
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+            const float c = max_norm / (norm + 1e-6f);
+            clip_s = c < 1.f ? c : 1.f;
+            if (blockIdx.x == 0 && norm_out) norm_out[0] = norm;
+        }
+        __syncthreads();
+        clip = clip_s;
+    }
+    const ptt_optim_tensor t = tensors[tensor_of[blockIdx.x]];
+    if (t.group < 0 || t.group >= n_groups) return;                 // the host refuses these where it can see the table
+    const ptt_optim_hyper h = DEV ? h_device[t.group] : h_value.g[t.group];
+    const int64_t e0 = first[blockIdx.x], e1 = e0 + ADAM_CHUNK < t.n ? e0 + ADAM_CHUNK : t.n;
+    if (h.kind == PTT_OPTIM_SGD) {
+        const bool buffered = h.beta1 != 0.f;
+        if (buffered && !t.state1) return;
+        for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) {
+            const float g0 = t.grad[e] * clip;
+            const float p = t.param[e];
+            float g = g0;
+            if (h.weight_decay != 0.f) g = g + h.weight_decay * p;                           // grad.add(param, alpha=wd)
+            if (buffered) {
+                if (!h.first_step) g = t.state1[e] * h.beta1 + g;                            // buf.mul_(momentum).add_(grad)
+                t.state1[e] = g;
+            }
+            t.param[e] = p + (-h.step_size) * g;                                             // param.add_(buf, alpha=-lr)
+            if (write_clipped) t.grad[e] = g0;
+        }
+    } else if (h.kind == PTT_OPTIM_ADAM || h.kind == PTT_OPTIM_ADAMW) {
+        if (!t.state1 || !t.state2) return;
+        const bool decoupled = h.kind == PTT_OPTIM_ADAMW;
+        for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) {
+            const float g0 = t.grad[e] * clip;
+            float g = g0;
+            float p = t.param[e];
+            if (decoupled) p = p * h.decay;                                                  // param.mul_(1 - lr * weight_decay)
+            else if (h.weight_decay != 0.f) g = g + h.weight_decay * p;
+            const float m0 = t.state1[e], w = h.one_minus_beta1;                             // exp_avg.lerp_(grad, 1 - beta1)
+            const float m = w < 0.5f ? m0 + w * (g - m0) : g - (g - m0) * (1.f - w);
+            const float v = t.state2[e] * h.beta2 + (h.one_minus_beta2 * g) * g;             // mul_(beta2).addcmul_(g, g, 1 - beta2)
+            const float denom = sqrtf(v) / h.bias2_sqrt + h.eps;
+            t.state1[e] = m;
+            t.state2[e] = v;
+            t.param[e] = p - h.step_size * (m / denom);                                      // addcdiv_(exp_avg, denom, value=-step_size)
+            if (write_clipped) t.grad[e] = g0;
+        }
+    }
+}
+
+// what the host can refuse: the rows when the caller hands over their host copy, the entries when they are host memory
+static int optim_check(const char* what, const ptt_optim_tensor* tensors_device, const ptt_optim_tensor* rows, int n_tensors,
+                       const int32_t* chunk_tensor_device, const int64_t* chunk_first_device, int n_chunks, const ptt_optim_hyper* hyper,
+                       bool hyper_on_host, int n_groups, float max_norm, const double* partial, size_t partial_elems) {
+    if (n_chunks < 0 || n_tensors < 0 || !hyper) return fail(PTT_EINVAL, "%s: n_chunks=%d n_tensors=%d hyper=%p", what, n_chunks, n_tensors, (const void*)hyper);
+    if (n_groups < 1) return fail(PTT_EINVAL, "%s: n_groups=%d", what, n_groups);
+    if (n_groups > PTT_OPTIM_MAX_GROUPS) return fail(PTT_EUNSUPPORTED, "%s: n_groups=%d (at most %d)", what, n_groups, PTT_OPTIM_MAX_GROUPS);
+    if (n_chunks > 0 && (!tensors_device || !chunk_tensor_device || !chunk_first_device)) return fail(PTT_EINVAL, "%s: null table", what);
+    if (hyper_on_host)
+        for (int g = 0; g < n_groups; ++g) {
+            const ptt_optim_hyper& h = hyper[g];
+            if (h.kind != PTT_OPTIM_ADAM && h.kind != PTT_OPTIM_ADAMW && h.kind != PTT_OPTIM_SGD)
+                return fail(PTT_EINVAL, "%s: group %d of unknown kind %d", what, g, h.kind);
+            if (h.kind != PTT_OPTIM_SGD && (!(h.bias2_sqrt > 0.f) || !(h.eps >= 0.f)))
+                return fail(PTT_EINVAL, "%s: group %d bias2_sqrt=%g eps=%g", what, g, (double)h.bias2_sqrt, (double)h.eps);
+        }
+    if (rows)
+        for (int k = 0; k < n_tensors; ++k) {
+            const ptt_optim_tensor& r = rows[k];
+            if (r.group < 0 || r.group >= n_groups) return fail(PTT_EINVAL, "%s: row %d in group %d of %d", what, k, r.group, n_groups);
+            if (!r.param || !r.grad || r.n < 0) return fail(PTT_EINVAL, "%s: row %d param=%p grad=%p n=%lld", what, k, (void*)r.param, (void*)r.grad, (long long)r.n);
+            if (!hyper_on_host) continue;
+            const ptt_optim_hyper& h = hyper[r.group];
+            if (h.kind == PTT_OPTIM_SGD ? (h.beta1 != 0.f && !r.state1) : (!r.state1 || !r.state2))
+                return fail(PTT_EINVAL, "%s: row %d (group %d, kind %d) lacks a state tensor", what, k, r.group, h.kind);
+        }
+    if (n_chunks > 0 && max_norm > 0.f && (!partial || partial_elems < (size_t)n_chunks))
+        return fail(PTT_EWORKSPACE, "%s: %d partial sums needed", what, n_chunks);
+    return PTT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -285,7 +394,7 @@ extern "C" int ptt_adam_clip_step_f32(const ptt_adam_tensor* tensors_device, con
     hipStream_t s = as_stream(stream);
     if (hyper->max_norm > 0.f) {
         if (!partial || partial_elems < (size_t)n_chunks) return fail(PTT_EWORKSPACE, "ptt_adam_clip_step_f32: %d partial sums needed", n_chunks);
-        hipLaunchKernelGGL(grad_sqsum_kernel, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device, partial);
+        hipLaunchKernelGGL(grad_sqsum_kernel<ptt_adam_tensor>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device, partial);
         if (int rc = check_launch("grad_sqsum_kernel")) return rc;
     }
     hipLaunchKernelGGL(adam_update_kernel<false>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device,
@@ -302,12 +411,50 @@ extern "C" int ptt_adam_clip_step_dev_f32(const ptt_adam_tensor* tensors_device,
     hipStream_t s = as_stream(stream);
     if (clip) {
         if (!partial || partial_elems < (size_t)n_chunks) return fail(PTT_EWORKSPACE, "ptt_adam_clip_step_dev_f32: %d partial sums needed", n_chunks);
-        hipLaunchKernelGGL(grad_sqsum_kernel, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device, partial);
+        hipLaunchKernelGGL(grad_sqsum_kernel<ptt_adam_tensor>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device, partial);
         if (int rc = check_launch("grad_sqsum_kernel")) return rc;
     }
     hipLaunchKernelGGL(adam_update_kernel<true>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device,
                        partial, n_chunks, ptt_adam_hyper{}, hyper_device, norm_out);
     return check_launch("adam_update_kernel");
+}
+
+extern "C" int ptt_optim_clip_step_f32(const ptt_optim_tensor* tensors_device, const ptt_optim_tensor* tensors_host, int n_tensors,
+                                       const int32_t* chunk_tensor_device, const int64_t* chunk_first_device, int n_chunks,
+                                       const ptt_optim_hyper* hyper, int n_groups, float max_norm, int write_clipped, double* partial,
+                                       size_t partial_elems, float* norm_out, ptt_stream_t stream) {
+    if (int rc = optim_check("ptt_optim_clip_step_f32", tensors_device, tensors_host, n_tensors, chunk_tensor_device, chunk_first_device,
+                             n_chunks, hyper, true, n_groups, max_norm, partial, partial_elems)) return rc;
+    if (n_chunks == 0) return PTT_OK;
+    hipStream_t s = as_stream(stream);
+    if (max_norm > 0.f) {
+        hipLaunchKernelGGL(grad_sqsum_kernel<ptt_optim_tensor>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device,
+                           chunk_first_device, partial);
+        if (int rc = check_launch("grad_sqsum_kernel")) return rc;
+    }
+    optim_groups groups{};
+    for (int g = 0; g < n_groups; ++g) groups.g[g] = hyper[g];
+    hipLaunchKernelGGL(optim_update_kernel<false>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device,
+                       partial, n_chunks, groups, (const ptt_optim_hyper*)nullptr, n_groups, max_norm, write_clipped, norm_out);
+    return check_launch("optim_update_kernel");
+}
+
+extern "C" int ptt_optim_clip_step_dev_f32(const ptt_optim_tensor* tensors_device, const ptt_optim_tensor* tensors_host, int n_tensors,
+                                           const int32_t* chunk_tensor_device, const int64_t* chunk_first_device, int n_chunks,
+                                           const ptt_optim_hyper* hyper_device, int n_groups, float max_norm, int write_clipped,
+                                           double* partial, size_t partial_elems, float* norm_out, ptt_stream_t stream) {
+    if (int rc = optim_check("ptt_optim_clip_step_dev_f32", tensors_device, tensors_host, n_tensors, chunk_tensor_device, chunk_first_device,
+                             n_chunks, hyper_device, false, n_groups, max_norm, partial, partial_elems)) return rc;
+    if (n_chunks == 0) return PTT_OK;
+    hipStream_t s = as_stream(stream);
+    if (max_norm > 0.f) {
+        hipLaunchKernelGGL(grad_sqsum_kernel<ptt_optim_tensor>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device,
+                           chunk_first_device, partial);
+        if (int rc = check_launch("grad_sqsum_kernel")) return rc;
+    }
+    hipLaunchKernelGGL(optim_update_kernel<true>, dim3(n_chunks), dim3(256), 0, s, tensors_device, chunk_tensor_device, chunk_first_device,
+                       partial, n_chunks, optim_groups{}, hyper_device, n_groups, max_norm, write_clipped, norm_out);
+    return check_launch("optim_update_kernel");
 }
 
 extern "C" int ptt_unit_rows_f32(const float* x, long long sb, long long sn, long long sc, int B, int n, int C, float eps, float* unit,

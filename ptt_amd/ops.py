@@ -8,6 +8,7 @@ synchronises. The second group exposes the fused fp32-MFMA kernels.
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import torch
@@ -2026,7 +2027,29 @@ def track_losses_bwd(out8, upstream, seed_cls, cls_label, search_inds, votes, re
     return g_cls, g_votes, g_box
 
 
-class AdamTable(object):
+class _GradPointerTable(object):
+    """What AdamTable and OptimTable share: rows in one pinned host copy (self.host / self.rows), uploaded to self.table whenever
+    the gradient pointers moved (autograd allocates new .grad tensors after zero_grad(set_to_none=True))."""
+
+    def _refresh_grads(self, grads, who):
+        for g, p in zip(grads, self.keep[0]):
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != p.numel() or g.device != self.device:
+                raise ValueError("%s.step: contiguous float32 gradients of the parameters' sizes expected" % who)
+        ptrs = [g.data_ptr() for g in grads]
+        if ptrs != self.grad_ptrs:                             # gradients that live in one place (train_ops.GradSink's views): one upload ever
+            self.uploaded.synchronize()                        # the previous step's upload has left the pinned table
+            for r, ptr in zip(self.rows, ptrs):
+                r.grad = ptr
+            self.table.copy_(self.host, non_blocking=True)
+            self.uploaded.record()
+            self.grad_ptrs = ptrs
+
+    def check_grads_in_place(self, grads):
+        """The table as uploaded addresses exactly these gradients (True once a step() saw them and they have not moved)."""
+        return self.grad_ptrs is not None and [g.data_ptr() for g in grads] == self.grad_ptrs
+
+
+class AdamTable(_GradPointerTable):
     """The device table ptt_adam_clip_step_f32 walks: parameters, their moments and the chunk map are fixed, the gradient
     pointers are refreshed every step (autograd allocates new .grad tensors after zero_grad(set_to_none=True)) through one
     pinned host copy of the table."""
@@ -2058,17 +2081,7 @@ class AdamTable(object):
         self.grad_ptrs = None
 
     def step(self, grads, beta1, beta2, eps, step_size, bias2_sqrt, weight_decay=0.0, max_norm=0.0, write_clipped=True):
-        for g, p in zip(grads, self.keep[0]):
-            if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != p.numel() or g.device != self.device:
-                raise ValueError("AdamTable.step: contiguous float32 gradients of the parameters' sizes expected")
-        ptrs = [g.data_ptr() for g in grads]
-        if ptrs != self.grad_ptrs:                             # gradients that live in one place (train_ops.GradSink's views): one upload ever
-            self.uploaded.synchronize()                        # the previous step's upload has left the pinned table
-            for r, ptr in zip(self.rows, ptrs):
-                r.grad = ptr
-            self.table.copy_(self.host, non_blocking=True)
-            self.uploaded.record()
-            self.grad_ptrs = ptrs
+        self._refresh_grads(grads, "AdamTable")
         h = self.hyper(beta1, beta2, eps, step_size, bias2_sqrt, weight_decay, max_norm, write_clipped)
         _launch("ptt_adam_clip_step_f32", self.device, _ptr(self.table), _ptr(self.which), _ptr(self.first), self.n_chunks, ctypes.byref(h),
                 _ptr(self.partial), self.partial.numel(), _ptr(self.norm))
@@ -2078,10 +2091,6 @@ class AdamTable(object):
     def hyper(beta1, beta2, eps, step_size, bias2_sqrt, weight_decay=0.0, max_norm=0.0, write_clipped=True):
         return _lib.AdamHyper(float(beta1), float(beta2), 1.0 - float(beta1), 1.0 - float(beta2), float(eps), float(step_size), float(bias2_sqrt),
                               float(weight_decay), float(max_norm), 1 if write_clipped else 0)
-
-    def check_grads_in_place(self, grads):
-        """The table as uploaded addresses exactly these gradients (True once a step() saw them and they have not moved)."""
-        return self.grad_ptrs is not None and [g.data_ptr() for g in grads] == self.grad_ptrs
 
     def step_device_hyper(self, hyper_device, clip):
         """The two launches of step() with the hyper-parameters read from `hyper_device` (AdamHyperRing.dev) when they RUN: what
@@ -2098,8 +2107,8 @@ class AdamHyperRing(object):
     `slots` steps ahead of the device; the slot's previous upload is waited for before it is rewritten) copied into ONE device
     struct on the stream the step runs on."""
 
-    def __init__(self, device, slots=64):
-        n = ctypes.sizeof(_lib.AdamHyper)
+    def __init__(self, device, slots=64, nbytes=None):
+        n = ctypes.sizeof(_lib.AdamHyper) if nbytes is None else int(nbytes)      # nbytes: an OptimHyper array (OptimTable)
         self.host = torch.zeros((slots, n), dtype=torch.uint8).pin_memory()
         self.dev = torch.zeros((n,), dtype=torch.uint8, device=device)
         self.events = [None] * slots
@@ -2109,12 +2118,83 @@ class AdamHyperRing(object):
         s = self.k % len(self.events)
         if self.events[s] is not None:
             self.events[s].synchronize()
-        ctypes.memmove(self.host[s].data_ptr(), ctypes.byref(h), ctypes.sizeof(_lib.AdamHyper))
+        ctypes.memmove(self.host[s].data_ptr(), ctypes.byref(h), ctypes.sizeof(h))
         self.dev.copy_(self.host[s], non_blocking=True)
         ev = self.events[s] or torch.cuda.Event()
         ev.record()
         self.events[s] = ev
         self.k += 1
+
+
+class OptimTable(_GradPointerTable):
+    """The device table ptt_optim_clip_step_f32 walks: AdamTable with a group index and up to two state tensors per row
+    (exp_avg, exp_avg_sq | momentum_buffer, None | None, None). `groups[k]` is row k's index into the hyper-parameter array."""
+
+    def __init__(self, params, state1, state2, groups, n_groups):
+        self.device = params[0].device
+        if not 1 <= n_groups <= _lib.PTT_OPTIM_MAX_GROUPS:
+            raise ValueError("OptimTable: 1 .. %d parameter groups expected, got %d" % (_lib.PTT_OPTIM_MAX_GROUPS, n_groups))
+        chunk = _host("ptt_adam_chunk_elems")
+        n = len(params)
+        self.n_groups = n_groups
+        self.host = torch.zeros((n, ctypes.sizeof(_lib.OptimTensor)), dtype=torch.uint8).pin_memory()
+        self.rows = (_lib.OptimTensor * n).from_address(self.host.data_ptr())
+        which, first = [], []
+        for k, (p, a, b, g) in enumerate(zip(params, state1, state2, groups)):
+            for t in (p, a, b):
+                if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or t.numel() != p.numel()):
+                    raise ValueError("OptimTable: contiguous float32 tensors of the parameter's size on one device expected")
+            r = self.rows[k]
+            r.param, r.n, r.group = p.data_ptr(), p.numel(), int(g)
+            r.state1, r.state2 = (a.data_ptr() if a is not None else None), (b.data_ptr() if b is not None else None)
+            for e in range(0, p.numel(), chunk):
+                which.append(k)
+                first.append(e)
+        self.n_chunks = len(which)
+        self.which = torch.tensor(which, dtype=torch.int32, device=self.device)
+        self.first = torch.tensor(first, dtype=torch.int64, device=self.device)
+        self.table = torch.empty_like(self.host, device=self.device)
+        self.partial = torch.empty((max(1, self.n_chunks),), dtype=torch.float64, device=self.device)
+        self.norm = torch.zeros((1,), dtype=torch.float32, device=self.device)
+        self.keep = (list(params), list(state1), list(state2))
+        self.uploaded = torch.cuda.Event()
+        self.grad_ptrs = None
+
+    @staticmethod
+    def hyper(kind, lr, t=1, betas=(0.0, 0.0), eps=0.0, weight_decay=0.0, momentum=0.0, first_step=False):
+        """One group's ptt_optim_hyper from an optimizer's own values; t = the step count of the step about to run (Adam kinds).
+        Everything is formed in double as torch forms it and rounded once."""
+        if kind == "sgd":
+            return _lib.OptimHyper(_lib.OPTIM_KINDS[kind], 1 if first_step else 0, float(momentum), 0.0, 0.0, 0.0, 0.0, float(lr), 1.0,
+                                   float(weight_decay), 1.0, 0)
+        beta1, beta2 = float(betas[0]), float(betas[1])
+        decoupled = kind == "adamw"
+        return _lib.OptimHyper(_lib.OPTIM_KINDS[kind], 0, beta1, beta2, 1.0 - beta1, 1.0 - beta2, float(eps), float(lr) / (1.0 - beta1 ** t),
+                               math.sqrt(1.0 - beta2 ** t), 0.0 if decoupled else float(weight_decay),
+                               1.0 - float(lr) * float(weight_decay) if decoupled else 1.0, 0)
+
+    def hyper_array(self, hypers):
+        if len(hypers) != self.n_groups:
+            raise ValueError("OptimTable: %d hyper-parameter entries for %d groups" % (len(hypers), self.n_groups))
+        return (_lib.OptimHyper * self.n_groups)(*hypers)
+
+    def step(self, grads, hypers, max_norm=0.0, write_clipped=True):
+        """clip (max_norm > 0) + update, two launches; hypers: one OptimTable.hyper(...) per group. Returns the (1,) norm tensor."""
+        self._refresh_grads(grads, "OptimTable")
+        _launch("ptt_optim_clip_step_f32", self.device, _ptr(self.table), self.host.data_ptr(), len(self.rows), _ptr(self.which), _ptr(self.first),
+                self.n_chunks, self.hyper_array(hypers), self.n_groups, float(max_norm), 1 if write_clipped else 0, _ptr(self.partial),
+                self.partial.numel(), _ptr(self.norm))
+        return self.norm
+
+    def step_device_hyper(self, hyper_device, max_norm=0.0, write_clipped=True):
+        """The two launches with the groups' entries read from `hyper_device` (an AdamHyperRing of n_groups OptimHyper) when
+        they RUN: what a captured training step records."""
+        if self.grad_ptrs is None:
+            raise RuntimeError("OptimTable.step_device_hyper: step() must have run once (the gradient addresses are uploaded then)")
+        _launch("ptt_optim_clip_step_dev_f32", self.device, _ptr(self.table), self.host.data_ptr(), len(self.rows), _ptr(self.which),
+                _ptr(self.first), self.n_chunks, _ptr(hyper_device), self.n_groups, float(max_norm), 1 if write_clipped else 0,
+                _ptr(self.partial), self.partial.numel(), _ptr(self.norm))
+        return self.norm
 
 
 def unit_rows_eps(x, eps):

@@ -109,14 +109,19 @@ class DataParallelTrainer(object):
     """
 
     def __init__(self, model, device, lr=1e-3, betas=(0.5, 0.999), eps=1e-6, clip=10.0, bucket_cap_mb=25, sync_bn=False, force_ddp=False,
-                 reducer=None, graph=None, graph_warmup=3):
+                 reducer=None, graph=None, graph_warmup=3, optimizer=None, scheduler=None):
         """graph: None = replay the step as hipGraphs where that is possible (HIP device, flat reducer, no SyncBatchNorm exchange;
         anything else steps eagerly), True = the same but raise where it is not possible, False = always eager. graph_warmup:
         eager steps before the capture (the plans, tables and workspaces of a step are built by them).
         force_ddp: reduce the gradients over the process group whenever one is initialised, a ONE-rank group included (the
         all-reduce then runs on the device with one participant: how a one-GPU box exercises the multi-GPU code).
         reducer: "flat" (HIP devices, the default there) = train_ops.GradSink + one all-reduce over its buffer; "ddp" =
-        DistributedDataParallel (the default, and the only choice, off the HIP device)."""
+        DistributedDataParallel (the default, and the only choice, off the HIP device).
+        optimizer: None = ClipAdam(lr, betas, eps); otherwise an optimizer instance over the model's parameters or a callable
+        model -> optimizer (ptt_amd.optimization.build_optimizer gives the ones of a config's OPTIMIZATION block). One without
+        the capture protocol of ptt_amd.optim (a stock torch optimizer) steps eagerly after `clip_grad_norm_`.
+        scheduler: an object whose .step(it) is called with the running iteration count at the top of every step(), before the
+        optimizer's host half reads lr / betas / momentum (tools/train_utils/train_utils.py:26-27)."""
         self.device = torch.device(device)
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         collective = self.world > 1 or (force_ddp and dist.is_available() and dist.is_initialized())
@@ -141,7 +146,16 @@ class DataParallelTrainer(object):
         else:
             self.model = model
         # torch.optim.Adam with clip_grad_norm_ folded into step(): two launches on a HIP device, the stock path elsewhere
-        self.optimizer = ClipAdam(self.model.parameters(), lr=lr, betas=betas, eps=eps)
+        if optimizer is None:
+            self.optimizer = ClipAdam(self.model.parameters(), lr=lr, betas=betas, eps=eps)
+        elif isinstance(optimizer, torch.optim.Optimizer):
+            self.optimizer = optimizer
+        else:
+            self.optimizer = optimizer(self.model)
+        self.scheduler = scheduler
+        self.epoch_scheduler = None       # from_optim_cfg: a per-epoch schedule ('step'), stepped by the caller
+        self.iteration = 0                # steps taken: what scheduler.step() is called with
+        self._fused_clip = hasattr(self.optimizer, "prepare_graph_step")      # ptt_amd.optim: step(max_norm=...) clips
         self.clip = clip
         self.sink = None
         if reducer == "flat":
@@ -152,7 +166,9 @@ class DataParallelTrainer(object):
         can_graph = reducer == "flat" and not (sync_bn and self.world > 1)
         if graph and not can_graph:
             raise ValueError("graph=True needs the flat reducer on a HIP device and no SyncBatchNorm exchange inside the step")
-        self.graph_mode = can_graph and graph is not False and os.environ.get("PTT_TRAIN_GRAPH", "1") != "0"
+        if graph and not self._fused_clip:
+            raise ValueError("graph=True needs an optimizer of ptt_amd.optim (the capture protocol); this one steps eagerly")
+        self.graph_mode = can_graph and self._fused_clip and graph is not False and os.environ.get("PTT_TRAIN_GRAPH", "1") != "0"
         self.graph_warmup = max(1, int(graph_warmup))
         self.eager_steps = 0
         self.captured = None              # _CapturedStep once the step has been captured
@@ -199,6 +215,9 @@ class DataParallelTrainer(object):
     def step(self, batch):
         """One training step; returns the loss (a 0-dim device tensor — in graph mode the SAME tensor every step, holding the
         latest step's value once the device gets there)."""
+        if self.scheduler is not None:
+            self.scheduler.step(self.iteration)
+        self.iteration += 1
         if self.graph_mode:
             if self.captured is not None and not self.captured.valid(self):
                 self.captured = None                          # e.g. optimizer.load_state_dict(): new moment tensors
@@ -207,10 +226,27 @@ class DataParallelTrainer(object):
             if self.captured is not None and self.captured.accepts(batch):
                 return self._replay(batch)
         loss = self.forward_backward(batch)
-        self.optimizer.step(max_norm=self.clip if self.clip else None)
+        if self._fused_clip:
+            self.optimizer.step(max_norm=self.clip if self.clip else None)
+        else:
+            if self.clip:
+                torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
+            self.optimizer.step()
         self.tracker.update_global_step()
         self.eager_steps += 1
         return loss
+
+    @classmethod
+    def from_optim_cfg(cls, model, device, optim_cfg, total_iters_each_epoch, total_epochs, **kw):
+        """The trainer of a config's OPTIMIZATION block: build_optimizer / build_scheduler of ptt_amd.optimization and
+        GRAD_NORM_CLIP (tools/train_tracking.py:161-167 with train_utils.py:26-51). kw: the other constructor arguments."""
+        from .optimization import build_optimizer, build_scheduler
+        trainer = cls(model, device, clip=optim_cfg.get('GRAD_NORM_CLIP', 10.0), optimizer=lambda m: build_optimizer(m, optim_cfg), **kw)
+        sched, _ = build_scheduler(trainer.optimizer, total_iters_each_epoch, total_epochs, -1, optim_cfg)
+        # OneCycle (no SCHEDULER key) is stepped per iteration, by step(); a 'step' schedule per EPOCH, by the caller's loop
+        # (train_utils.py:116-117): trainer.epoch_scheduler.step() after each epoch
+        trainer.scheduler, trainer.epoch_scheduler = (sched, None) if optim_cfg.get('SCHEDULER', None) is None else (None, sched)
+        return trainer
 
     # ------------------------------------------------------------------------------------------------ the captured step
     def _capture(self, batch):
