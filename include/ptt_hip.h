@@ -903,12 +903,15 @@ int ptt_bn_update_running_f32(const float* mean, const float* var, const double*
 /* CosineSimAug's first convolution in training mode with its similarity channel split off (p2b_xcoor.py:35-40):
  * z0[b,j,i,:] = P[b,i,:] + cos_t[b,j,i] * w_sim[:]  (rows ordered (b, j, i): search point j, template point i), and its
  * backward in one pass over dz0: dP[b,i,:] = sum_j dz0, dcos[b,j,i] = <dz0[b,j,i,:], w_sim>, dw[:] = sum dz0 * cos_t
- * (fixed summation order). C % 4 == 0; the backward needs C <= 256. */
+ * (fixed summation order). C % 4 == 0; the backward needs C <= 256 (PTT_EINVAL otherwise). */
 int ptt_xcorr_z0_f32(const float* P, const float* cos_t, const float* w_sim, int B, int n2, int n1, int C, float* z0, ptt_stream_t stream);
-/* the same launch also sums z0's BatchNorm statistics: float64 partials (chunks, 2, C), chunks = ptt_xcorr_z0_stat_chunks(...) */
+/* the same launch also sums z0's BatchNorm statistics: float64 partials (chunks, 2, C), chunks = ptt_xcorr_z0_stat_chunks(...);
+ * at most 1024 channels (PTT_EUNSUPPORTED otherwise, and the chunk query returns 0); fewer than chunks * 2 * C partial_elems:
+ * PTT_EWORKSPACE */
 int ptt_xcorr_z0_stat_chunks(int B, int n2, int n1, int C);
 int ptt_xcorr_z0_stats_f32(const float* P, const float* cos_t, const float* w_sim, int B, int n2, int n1, int C, float* z0,
                            double* stats_partial, size_t partial_elems, ptt_stream_t stream);
+/* both backward forms take a workspace of at least ptt_xcorr_z0_bwd_workspace(B, n1, C) bytes (PTT_EWORKSPACE otherwise) */
 size_t ptt_xcorr_z0_bwd_workspace(int B, int n1, int C);
 /* ptt_xcorr_z0_bwd_f32 when dz0 does not exist yet: G = the gradient w.r.t. relu(BatchNorm(z0)) as ptt_rows_gemm_bnbwd_f32 left it,
  * with that launch's partial sums; layer 0's BatchNorm + ReLU backward is applied while G is read and z0 is recomputed from
@@ -936,13 +939,14 @@ int ptt_xcorr_z0_bwd_f32(const float* dz0, const float* cos_t, const float* w_si
  *     pointnet2_utils.py:350-354 — and z0 = term[b,n,:] + Wx . rel, the first SharedMLP convolution (pytorch_utils.py:12-36;
  *     channel order xyz first, pointnet2_utils.py:359-361) with its feature half `term` (B,N,C) evaluated once per point;
  *     term NULL: a level without point features. z0 (B*M*ns, C) rows, rel_rows (B*M*ns, 3) (the weight gradient of Wx
- *     (C,3), row stride ldw >= 3, needs them). C % 4 == 0. No gradient w.r.t. the coordinates is provided: callers with
+ *     (C,3), row stride ldw >= 3, needs them). C % 4 == 0, radius > 0 (PTT_EINVAL otherwise); at most (2^31 - 1) / 4 rows per
+ *     cloud (PTT_EUNSUPPORTED otherwise). No gradient w.r.t. the coordinates is provided: callers with
  *     learnable coordinates (the box head's vote aggregation) keep ptt_group_f32 + ptt_gather_rows_f32. */
 int ptt_sa_z0_rows_f32(const float* xyz, const float* new_xyz, const int32_t* idx, const float* term, const float* wx, int ldw, int B,
                        int N, int M, int ns, int C, float radius, int normalize_xyz, float* z0, float* rel_rows, ptt_stream_t stream);
 /* The same launch also summing the BatchNorm statistics of layer 0 (the float64 column sums / sums of squares of z0) as
  * partials (chunks, 2, C), chunks = ptt_sa_z0_rows_stat_chunks(B, M, ns, C), for ptt_bn_finish_partials_f32 (or its _train form) — no
- * statistics pass over z0. C <= 1024. */
+ * statistics pass over z0. C <= 1024 (PTT_EUNSUPPORTED otherwise, and the chunk query returns 0). */
 int ptt_sa_z0_rows_stat_chunks(int B, int M, int ns, int C);
 int ptt_sa_z0_rows_stats_f32(const float* xyz, const float* new_xyz, const int32_t* idx, const float* term, const float* wx, int ldw, int B,
                              int N, int M, int ns, int C, float radius, int normalize_xyz, float* z0, float* rel_rows,

@@ -1379,7 +1379,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
             const f32x4t pv = *reinterpret_cast<const f32x4t*>(pos + (pt * KN + j) * D + c);
             f32x4t o;
 #pragma unroll
-            for (int x = 0; x < 4; ++x) { dat[j][x] = g[x] * (vv[x] + pv[x]); s[x] += w[j][x] * dat[j][x]; o[x] = w[j][x] * g[x]; }
+            for (int x = 0; x < 4; ++x) {
+                {
+                    // rounded once, for both of its uses: fused into `dat - s` below, the product stayed unrounded there while the
+                    // sum s held the rounded one, and a one-hot softmax (s == dat) gave da = the rounding error instead of 0
+#pragma clang fp contract(off)
+                    dat[j][x] = g[x] * (vv[x] + pv[x]);
+                }
+                s[x] += w[j][x] * dat[j][x]; o[x] = w[j][x] * g[x];
+            }
             *reinterpret_cast<f32x4t*>(dvp + (pt * KN + j) * D + c) = o;
         }
 #pragma unroll

@@ -14,8 +14,11 @@ Shapes: B = 3 with one duplicated cloud (cloud 1 repeats cloud 0) and one all-ze
 {16, 32}, k = 16, C in {4, 131} (the row kernels need C % 4 == 0: {4, 132}); the CSR pair at (N, E) = (100, 37) and
 (2049, 4096) — the second takes the bitonic path above 2048 bins.
 
-Out of scope: the training-only kernels (xcorr_z0*, sa_z0*, step_ops, track_ops, train_feed); the fused SA / xcorr / pair
-kernels are in tests/test_fused_guard_gpu.py, the row kernels in tests/test_strided_guard_gpu.py."""
+The training-only row kernels (xcorr_z0*, sa_z0*, the partial-sum finishers, pt_attn_train_bwd, unit_rows / cos_bwd_rows) are in
+tests/test_train_rows_guard_gpu.py, the fused SA / xcorr / pair kernels in tests/test_fused_guard_gpu.py, the row kernels in
+tests/test_strided_guard_gpu.py. Out of scope of the guard-band files: track_losses*, the optimizer step, track_ops.hip and
+train_feed, which have value tests of their own in tests/test_step_ops_gpu.py, tests/test_optimization_gpu.py,
+tests/test_tracking_gpu.py and tests/test_train_feed_gpu.py."""
 import numpy as np
 import pytest
 import torch
