@@ -529,7 +529,9 @@ int ptt_crop_scan_f32(const ptt_crop_job* jobs_device, int n_jobs, int max_point
  * outputs of MT19937(seed 1) masked to the smallest 2^k - 1 >= n - 1 and skipped while > n - 1. `draws` (DEVICE) holds
  * the generator's first n_draws outputs: fill a host buffer with ptt_mt19937_fill(1, ...) and upload it once;
  * n_draws >= 4 * input_size + 1024 always suffices (acceptance probability > 1/2). info (2 x int32, may be NULL)
- * receives n and the number of generator outputs consumed (0 when nothing was drawn). */
+ * receives n and the number of generator outputs consumed (0 when nothing was drawn). A draw table that runs out before
+ * input_size indices were accepted leaves the rows in front valid (those the table did yield), every row from the
+ * shortfall on NaN, and info[1] = -1. */
 #define PTT_MAX_SEGMENTS 4
 typedef struct ptt_regularize_job {
     const float* seg[PTT_MAX_SEGMENTS];          /* (seg_count, 3) float32 each */
@@ -587,7 +589,8 @@ int ptt_track_select_update(const float* proposals_host, int P, const int32_t* i
 
 /* ptt_select_box_f32 — post_process (eval_tracking_utils.py:266-274): for every frame b the row of
  * pred_box_data (B,P,5) with the largest score (column 4; first one among equals, as np.argmax) -> out (B,5);
- * idx_out (B) receives its index, or NULL. */
+ * idx_out (B) receives its index, or NULL. A NaN score counts as the maximum, again as np.argmax: the first NaN of a row wins,
+ * which is also what ptt_track_select_update chooses on the host. Every score -inf: row 0. */
 int ptt_select_box_f32(const float* pred_box_data, int B, int P, float* out, int32_t* idx_out, ptt_stream_t stream);
 
 /* ptt_box_overlap_f64 (ABI 27) — the two numbers the reference scores a tracked frame by (tools/eval_utils/

@@ -300,15 +300,18 @@ __global__ __launch_bounds__(256) void select_box_kernel(const float* __restrict
     if (b >= B) return;
     const float* row = boxes + (size_t)b * P * 5;
     float best = -__builtin_inff();
-    int bi = 0x7fffffff;
+    int bi = 0x7fffffff, nan_i = 0x7fffffff;
     for (int p = lane; p < P; p += 64) {
         const float s = row[(size_t)p * 5 + 4];
         if (s > best) { best = s; bi = p; }             // strict: the lowest index of a lane's equal maxima stays
+        if (s != s && p < nan_i) nan_i = p;             // np.argmax: a NaN is the maximum, the first one wins
     }
     const float m = wave_max_f32(best);
     const int cand = (best == m) ? bi : 0x7fffffff;
     int win = wave_min_i32(cand);
-    if (win == 0x7fffffff) win = 0;                      // every score -inf / NaN: np.argmax of all-equal gives 0
+    const int first_nan = wave_min_i32(nan_i);
+    if (first_nan != 0x7fffffff) win = first_nan;        // as ptt_track_select_update on the host
+    if (win == 0x7fffffff) win = 0;                      // every score -inf: np.argmax of all-equal gives 0
     if (lane < 5) out[(size_t)b * 5 + lane] = row[(size_t)win * 5 + lane];
     if (lane == 0 && idx_out) idx_out[b] = win;
 }
