@@ -61,6 +61,22 @@ def tracking_modes(shape_aggregation="firstandprevious", ref_box="previous_resul
     raise ValueError("reference_BB must be set with previous_result/previous_gt/current_gt")
 
 
+def upload_clouds(clouds, dev):
+    """One tracklet's clouds ((3, N_i) float32 arrays / tensors) -> a list of device tensors whose rows are `stride(0)` apart and
+    whose points are adjacent; tensors already on `dev` in that layout are used in place."""
+    if all(isinstance(c, np.ndarray) for c in clouds) and len(clouds) > 0:
+        # host arrays: ONE upload per tracklet — the frames side by side in a (3, sum N_i) buffer, every frame a
+        # column range of it (the crop kernel takes the row stride) — instead of one small copy per frame
+        sizes = [c.shape[1] for c in clouds]
+        packed = torch.from_numpy(np.ascontiguousarray(np.concatenate([c[0:3] for c in clouds], axis=1), np.float32))
+        packed = packed.to(dev)                  # pageable copy: pinning a fresh buffer per tracklet costs more than it saves
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        return [packed[:, offs[i]:offs[i + 1]] for i in range(len(clouds))]
+    row = [(c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32)))
+           .to(dev, torch.float32) for c in clouds]
+    return [t if t.stride(1) == 1 else t.contiguous() for t in row]
+
+
 class _BoxedForward(object):
     """tracker forward + best-proposal selection as ONE capturable callable: (search, template) -> (B,5) rows, the best
     proposal of each frame picked on the device (ptt_select_box_f32) — or, select=False, all (B,P,5) proposals: at a handful of
@@ -143,18 +159,7 @@ class TrackletRunner(object):
         self.npts = np.zeros((T, B), np.int32)
         cap = 1
         for b, (clouds, _) in enumerate(tracklets):
-            if all(isinstance(c, np.ndarray) for c in clouds) and len(clouds) > 0:
-                # host arrays: ONE upload per tracklet — the frames side by side in a (3, sum N_i) buffer, every frame a
-                # column range of it (the crop kernel takes the row stride) — instead of one small copy per frame
-                sizes = [c.shape[1] for c in clouds]
-                packed = torch.from_numpy(np.ascontiguousarray(np.concatenate([c[0:3] for c in clouds], axis=1), np.float32))
-                packed = packed.to(dev)                  # pageable copy: pinning a fresh buffer per tracklet costs more than it saves
-                offs = np.concatenate([[0], np.cumsum(sizes)])
-                row = [packed[:, offs[i]:offs[i + 1]] for i in range(len(clouds))]
-            else:
-                row = [(c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32)))
-                       .to(dev, torch.float32) for c in clouds]
-                row = [t if t.stride(1) == 1 else t.contiguous() for t in row]
+            row = upload_clouds(clouds, dev)
             for i, t in enumerate(row):
                 self.ptr[i, b], self.ld[i, b], self.npts[i, b] = t.data_ptr(), t.stride(0), t.shape[1]
                 cap = max(cap, t.shape[1])
