@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 33
+#define PTT_ABI_VERSION 34
 
 enum {
     PTT_OK = 0,
@@ -521,6 +521,73 @@ int ptt_crop_compact_host_f32(const ptt_crop_job* jobs_host, int n_jobs, ptt_str
 #define PTT_SCAN_CROP_CHUNK 1024
 size_t ptt_crop_scan_workspace(int n_jobs, int max_points);
 int ptt_crop_scan_f32(const ptt_crop_job* jobs_device, int n_jobs, int max_points, void* ws, size_t ws_bytes, ptt_stream_t stream);
+
+/* ptt_scan_ingest_f32 (ABI 34) — the sensor's raw rows into planar clouds in the reference frame: what
+ * KittiTrackingDataset.get_lidar (ptt/datasets/kitti/kitti_dataset_tracking.py:298-308) does on the host with
+ * np.fromfile(...).reshape(-1, 4).T, PointCloud.__init__ (kitti_tracking_utils.py:10-13: the first three rows) and
+ * PointCloud.transform, and the nuScenes loader with rotate / translate / rotate / translate (nus_dataset_tracking.py:140-145).
+ *   Per point: p = raw[i * row_floats + 0..2]; the steps are applied in order. A step is computed in float64 from the float32 p,
+ *   every multiplication and addition rounded on its own (no fused multiply-add), and its result is rounded to float32 before
+ *   the next step — the reference stores every step back into its float32 array:
+ *     PTT_SCAN_ROTATE     p_r = float32((m[3r] * x + m[3r+1] * y) + m[3r+2] * z)                  m[0..8]  row-major 3x3
+ *     PTT_SCAN_TRANSLATE  p_r = float32(p_r + m[r])                                               m[0..2]
+ *     PTT_SCAN_AFFINE     p_r = float32(((m[4r] * x + m[4r+1] * y) + m[4r+2] * z) + m[4r+3])      m[0..11] row-major 3x4
+ *   n_steps = 0 is a pure de-interleave, bit-exact. A `kind` that is none of the three is applied as the identity, n_steps is
+ *   clamped to 0..PTT_SCAN_MAX_STEPS: the device cannot report what is inside the table, callers that hold the host table check
+ *   it before the launch (ops.scan_ingest_check raises ValueError).
+ *   The crop's own rotate (ptt_crop_compact_f32) forms the same sum with fused multiply-adds and is therefore NOT this function:
+ *   the two agree except where the un-fused float64 sum lies within one float64 ulp of a float32 rounding boundary.
+ *   Geometry: grid = (chunks of PTT_SCAN_CROP_CHUNK points of the longest job) x (jobs), one point per thread. max_points: the
+ *   host's upper bound on every job's n_points; points from max_points (rounded up to a whole chunk) on are not looked at.
+ *   Reads and writes: a job with n_points = 0 writes nothing; nothing outside out[r * ld + 0 .. n_points), r = 0..2, is written;
+ *   `raw` is read one float at a time unless row_floats == 4 and `raw` is 16-byte aligned (then one 16-byte load per point).
+ *   `jobs` may live in device memory or in PINNED host memory, as the crop table of ptt_crop_regularize_f32. One launch, no
+ *   workspace, no atomics, no host synchronisation; it can be captured in a graph.
+ *   PTT_EINVAL, before any runtime call: jobs == NULL, n_jobs outside 1..65535, max_points < 1 (or beyond 2^31 - 1 - chunk). */
+#define PTT_SCAN_MAX_STEPS 4
+#define PTT_SCAN_ROTATE    1
+#define PTT_SCAN_TRANSLATE 2
+#define PTT_SCAN_AFFINE    3
+typedef struct ptt_scan_step {
+    int32_t kind;               /* PTT_SCAN_ROTATE / _TRANSLATE / _AFFINE */
+    int32_t reserved;           /* 0 */
+    double m[12];
+} ptt_scan_step;
+typedef struct ptt_scan_job {
+    const float* raw;           /* (n_points, row_floats) float32, 4-byte aligned */
+    float* out;                 /* (3, n_points) planar, rows `ld` elements apart */
+    int64_t ld;
+    int32_t n_points;
+    int32_t row_floats;         /* 3..16; columns from 3 on (intensity, ring, time) are dropped */
+    int32_t n_steps;            /* 0..PTT_SCAN_MAX_STEPS */
+    int32_t reserved;           /* 0 */
+    ptt_scan_step steps[PTT_SCAN_MAX_STEPS];
+} ptt_scan_job;
+int ptt_scan_ingest_f32(const ptt_scan_job* jobs, int n_jobs, int max_points, ptt_stream_t stream);
+
+/* ptt_scan_preload_f32 (ABI 34) — crop_pc (kitti_tracking_utils.py:275-297) without a change of frame, planar in and planar
+ * out: the preload crop of get_lidar (kitti_dataset_tracking.py:309-310). Keeps the points with lo < p < hi on every axis (float32
+ * point against float64 bound, strict, :281-292); the host forms lo / hi from the box's corners -/+ offset (:276-279).
+ *   Survivors are written to `out` in their original order with their values unchanged; *count = their number, even above
+ *   `capacity`; columns from `capacity` on are not written; out == NULL only counts.
+ *   Two launches over grid = (chunks of PTT_SCAN_CROP_CHUNK points) x (jobs), exactly as ptt_crop_scan_f32 makes them: the first
+ *   writes the survivor count of every (job, chunk) into the workspace, the second adds up the counts of the chunks in front,
+ *   repeats the test and writes. No workgroup waits for another, nothing is placed by an atomic, a second call writes identical
+ *   bytes. The job table lives in DEVICE memory. max_points as for ptt_crop_scan_f32.
+ *   ws / ws_bytes: ptt_scan_preload_workspace(n_jobs, max_points) bytes of device memory, 4-byte aligned, overwritten by every call.
+ *   PTT_EINVAL, before any launch: a short or misaligned workspace, a null pointer, n_jobs outside 1..65535, max_points < 1. */
+typedef struct ptt_preload_job {
+    const float* points;        /* (3, n_points) planar float32, rows `ld` elements apart */
+    int64_t ld;
+    int32_t n_points;
+    int32_t capacity;
+    double lo[3], hi[3];
+    float* out;                 /* (3, capacity) planar, rows `out_ld` elements apart; NULL: count only */
+    int64_t out_ld;
+    int32_t* count;
+} ptt_preload_job;
+size_t ptt_scan_preload_workspace(int n_jobs, int max_points);
+int ptt_scan_preload_f32(const ptt_preload_job* jobs_device, int n_jobs, int max_points, void* ws, size_t ws_bytes, ptt_stream_t stream);
 
 /* ptt_regularize_f32 — one job = regularize_pc(pc, input_size, istrain=False) (kitti_tracking_utils.py:342-367) on the
  * concatenation of up to PTT_MAX_SEGMENTS compacted crops (get_model :219-236 concatenates the crops of several

@@ -93,6 +93,27 @@ class CropJob(Structure):
                 ("append", c_int32), ("reserved", c_int32)]
 
 
+PTT_SCAN_MAX_STEPS = DEFINES["PTT_SCAN_MAX_STEPS"]
+SCAN_KINDS = {"rotate": DEFINES["PTT_SCAN_ROTATE"], "translate": DEFINES["PTT_SCAN_TRANSLATE"], "affine": DEFINES["PTT_SCAN_AFFINE"]}
+
+
+class ScanStep(Structure):
+    """ptt_scan_step: one rotate / translate / affine of a scan's way into the reference frame."""
+    _fields_ = [("kind", c_int32), ("reserved", c_int32), ("m", c_double * 12)]
+
+
+class ScanJob(Structure):
+    """ptt_scan_job: one raw (n_points, row_floats) scan -> a planar (3, n_points) cloud; device or pinned host memory."""
+    _fields_ = [("raw", c_void_p), ("out", c_void_p), ("ld", c_int64), ("n_points", c_int32), ("row_floats", c_int32),
+                ("n_steps", c_int32), ("reserved", c_int32), ("steps", ScanStep * PTT_SCAN_MAX_STEPS)]
+
+
+class PreloadJob(Structure):
+    """ptt_preload_job: one crop_pc of a planar cloud in its own frame, planar output; arrays of these are uploaded to the device."""
+    _fields_ = [("points", c_void_p), ("ld", c_int64), ("n_points", c_int32), ("capacity", c_int32),
+                ("lo", c_double * 3), ("hi", c_double * 3), ("out", c_void_p), ("out_ld", c_int64), ("count", c_void_p)]
+
+
 class RegularizeJob(Structure):
     """ptt_regularize_job: regularize_pc over the concatenation of up to 4 compacted crops."""
     _fields_ = [("seg", c_void_p * PTT_MAX_SEGMENTS), ("seg_count", c_void_p * PTT_MAX_SEGMENTS),

@@ -15,6 +15,9 @@
 //   train_batch_kernel   N5: a training batch out of the crops of B + spare candidates (get_train_items, ptt/datasets/kitti/
 //                        kitti_dataset_tracking.py:60-179): validity, replacement of rejected samples by spares, and regularize_pc(istrain=
 //                        True) of search (+ labels) and template on counter-based Philox4x32-10 indices.
+//   scan_ingest_kernel   get_lidar's host pass (kitti_dataset_tracking.py:298-308): interleaved sensor rows -> planar (3, N) clouds,
+//                        through PointCloud.transform / rotate / translate chains, each step stored back as float32.
+//   scan_preload_*       get_lidar's preload crop (:309-310): crop_pc in the cloud's own frame, planar output, two launches.
 // Arithmetic follows numpy's: points are float32, box quantities float64; `translate` rounds (double)p + t to float32,
 // `rotate` rounds the float64 dot product to float32; comparisons are float32 point against float64 bound, strict.
 #include <math.h>
@@ -203,6 +206,106 @@ __global__ __launch_bounds__(kScanChunk) void crop_scan_write_kernel(const ptt_c
         }
     }
     if (last && threadIdx.x == 0) *j.count = first + own;               // may exceed capacity, as crop_compact_body's
+}
+
+// ---- ptt_scan_ingest_f32: raw (n, row_floats) rows -> planar (3, n) clouds in the reference frame, one point per thread ----
+// One step of the chain on one point: float64 from the float32 point, every product and sum rounded on its own (the file is
+// compiled with -ffp-contract=off and nothing here asks for an fma — unlike crop_point's rotate, which is why that one is not
+// reused), the result rounded to float32. An unknown kind leaves the point as it is.
+__device__ __forceinline__ void scan_step(const ptt_scan_step& s, float& x, float& y, float& z) {
+    const double dx = (double)x, dy = (double)y, dz = (double)z;
+    const double* m = s.m;
+    if (s.kind == PTT_SCAN_ROTATE) {                // PointCloud.rotate
+        x = (float)((m[0] * dx + m[1] * dy) + m[2] * dz);
+        y = (float)((m[3] * dx + m[4] * dy) + m[5] * dz);
+        z = (float)((m[6] * dx + m[7] * dy) + m[8] * dz);
+    } else if (s.kind == PTT_SCAN_TRANSLATE) {      // PointCloud.translate
+        x = (float)(dx + m[0]);
+        y = (float)(dy + m[1]);
+        z = (float)(dz + m[2]);
+    } else if (s.kind == PTT_SCAN_AFFINE) {         // PointCloud.transform: the fourth coordinate is 1
+        x = (float)(((m[0] * dx + m[1] * dy) + m[2] * dz) + m[3]);
+        y = (float)(((m[4] * dx + m[5] * dy) + m[6] * dz) + m[7]);
+        z = (float)(((m[8] * dx + m[9] * dy) + m[10] * dz) + m[11]);
+    }
+}
+
+// Workgroup (c, job) owns points [c * C, (c + 1) * C) of the job. Loads: a 4-float row on a 16-byte aligned base is one 16-byte
+// load per lane (a wave reads 1 KiB in one instruction); any other row is three 4-byte loads row_floats apart. Stores: three
+// planar rows, lane i next to lane i + 1. The job (uniform over the workgroup) is read through the scalar cache.
+__global__ __launch_bounds__(kScanChunk) void scan_ingest_kernel(const ptt_scan_job* __restrict__ jobs) {
+    const ptt_scan_job& j = jobs[blockIdx.y];
+    const int n = j.n_points;
+    const int i = (int)blockIdx.x * kScanChunk + (int)threadIdx.x;      // < max_points + C <= 2^31 - 1 (checked by the host)
+    if (i >= n) return;
+    const int C = j.row_floats;
+    float x, y, z;
+    if (C == 4 && ((uintptr_t)j.raw & 15u) == 0) {                      // uniform
+        const float4 v = reinterpret_cast<const float4*>(j.raw)[i];
+        x = v.x; y = v.y; z = v.z;
+    } else {
+        const float* p = j.raw + (size_t)i * (size_t)C;
+        x = p[0]; y = p[1]; z = p[2];
+    }
+    const int ns = min(max(j.n_steps, 0), PTT_SCAN_MAX_STEPS);
+    for (int k = 0; k < ns; ++k) scan_step(j.steps[k], x, y, z);
+    j.out[i] = x;
+    j.out[j.ld + i] = y;
+    j.out[2 * j.ld + i] = z;
+}
+
+// ---- ptt_scan_preload_f32: crop_pc in the cloud's own frame, planar in and out; the two launches of ptt_crop_scan_f32 ----
+__device__ __forceinline__ bool preload_keep(const ptt_preload_job& j, int i) {
+    const double x = (double)j.points[i], y = (double)j.points[j.ld + i], z = (double)j.points[2 * j.ld + i];
+    return x > j.lo[0] && x < j.hi[0] && y > j.lo[1] && y < j.hi[1] && z > j.lo[2] && z < j.hi[2];
+}
+
+__global__ __launch_bounds__(kScanChunk) void scan_preload_count_kernel(const ptt_preload_job* __restrict__ jobs, int32_t* __restrict__ counts) {
+    __shared__ int wsum[kScanChunk / 64];
+    const ptt_preload_job& j = jobs[blockIdx.y];
+    const int n = j.n_points;
+    const int base = (int)blockIdx.x * kScanChunk;
+    int32_t* slot = counts + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (base >= n) {                                                    // uniform: a chunk past this job's cloud
+        if (threadIdx.x == 0) *slot = 0;
+        return;
+    }
+    const int i = base + (int)threadIdx.x;
+    const bool keep = i < n && preload_keep(j, i);
+    int total;
+    block_rank<kScanChunk>(keep, wsum, total);
+    if (threadIdx.x == 0) *slot = total;
+}
+
+__global__ __launch_bounds__(kScanChunk) void scan_preload_write_kernel(const ptt_preload_job* __restrict__ jobs, const int32_t* __restrict__ counts) {
+    __shared__ int wsum[kScanChunk / 64];
+    const int32_t* c = counts + (size_t)blockIdx.y * gridDim.x;
+    const int own = c[blockIdx.x];
+    const bool last = blockIdx.x == gridDim.x - 1;
+    if (own == 0 && !last) return;                                      // uniform
+    int part = 0;
+    for (int k = threadIdx.x; k < (int)blockIdx.x; k += kScanChunk) part += c[k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
+    __syncthreads();
+    int first = 0;
+#pragma unroll
+    for (int w = 0; w < kScanChunk / 64; ++w) first += wsum[w];
+    __syncthreads();                                                    // block_rank reuses wsum
+    const ptt_preload_job& j = jobs[blockIdx.y];
+    if (own != 0 && j.out != nullptr) {                                 // uniform
+        const int i = (int)blockIdx.x * kScanChunk + (int)threadIdx.x;
+        const bool keep = i < j.n_points && preload_keep(j, i);
+        int total;
+        const int r = first + block_rank<kScanChunk>(keep, wsum, total);
+        if (keep && r < j.capacity) {
+            j.out[r] = j.points[i];
+            j.out[j.out_ld + r] = j.points[j.ld + i];
+            j.out[2 * j.out_ld + r] = j.points[2 * j.ld + i];
+        }
+    }
+    if (last && threadIdx.x == 0) *j.count = first + own;               // may exceed capacity
 }
 
 __device__ __forceinline__ void seg_point(const ptt_regularize_job& j, const int* cnt, int idx, float* dst) {
@@ -630,6 +733,28 @@ extern "C" int ptt_crop_scan_f32(const ptt_crop_job* jobs_device, int n_jobs, in
     hipLaunchKernelGGL(crop_scan_count_kernel, grid, dim3(kScanChunk), 0, as_stream(stream), jobs_device, counts);
     hipLaunchKernelGGL(crop_scan_write_kernel, grid, dim3(kScanChunk), 0, as_stream(stream), jobs_device, (const int32_t*)counts);
     return check_launch("crop_scan_kernel");
+}
+
+extern "C" int ptt_scan_ingest_f32(const ptt_scan_job* jobs, int n_jobs, int max_points, ptt_stream_t stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > 65535 || max_points < 1 || max_points > 0x7fffffff - kScanChunk)
+        return fail(PTT_EINVAL, "ptt_scan_ingest_f32: jobs=%p n_jobs=%d (1..65535) max_points=%d (>= 1)", (const void*)jobs, n_jobs, max_points);
+    hipLaunchKernelGGL(scan_ingest_kernel, dim3(scan_chunks(max_points), n_jobs), dim3(kScanChunk), 0, as_stream(stream), jobs);
+    return check_launch("scan_ingest_kernel");
+}
+
+extern "C" size_t ptt_scan_preload_workspace(int n_jobs, int max_points) { return ptt_crop_scan_workspace(n_jobs, max_points); }
+
+extern "C" int ptt_scan_preload_f32(const ptt_preload_job* jobs_device, int n_jobs, int max_points, void* ws, size_t ws_bytes, ptt_stream_t stream) {
+    if (!jobs_device || !ws || n_jobs < 1 || n_jobs > 65535 || max_points < 1 || max_points > 0x7fffffff - kScanChunk)
+        return fail(PTT_EINVAL, "ptt_scan_preload_f32: null job array or workspace, n_jobs=%d (1..65535) or max_points=%d (>= 1)", n_jobs, max_points);
+    const size_t need = ptt_scan_preload_workspace(n_jobs, max_points);
+    if (ws_bytes < need || ((uintptr_t)ws & 3u) != 0)
+        return fail(PTT_EINVAL, "ptt_scan_preload_f32: workspace of %zu bytes at %p, %zu bytes on a 4-byte boundary needed", ws_bytes, ws, need);
+    const dim3 grid(scan_chunks(max_points), n_jobs);
+    int32_t* counts = static_cast<int32_t*>(ws);
+    hipLaunchKernelGGL(scan_preload_count_kernel, grid, dim3(kScanChunk), 0, as_stream(stream), jobs_device, counts);
+    hipLaunchKernelGGL(scan_preload_write_kernel, grid, dim3(kScanChunk), 0, as_stream(stream), jobs_device, (const int32_t*)counts);
+    return check_launch("scan_preload_kernel");
 }
 
 extern "C" int ptt_crop_regularize_f32(const ptt_crop_job* crop_jobs, const ptt_regularize_job* reg_jobs_device, int n_jobs,

@@ -8,6 +8,7 @@ per target from its own detector at the moment the target appears. OnlineTracker
     boxes = ot.step(scan, add={7: (center, wlh, quat)})      # target 7 initialised on this scan: its frame 0
     boxes = ot.step(scan)                                    # {7: (center, wlh, quat, score)}
     boxes = ot.step(scan, add={9: ...}, drop=(7,))
+    boxes = ot.step_raw(raw, steps=[('affine', V2C)])        # the sensor's (N, C) rows: de-interleaved and transformed on the device
 
 What a step computes for a continuing target is what TrackletRunner._steps computes for frame i of a tracklet whose clouds are
 the scans since the target's `add`, with REF_BOX = previous_result — bit for bit, because it IS the runner's code: the same
@@ -32,6 +33,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .scene_store import check_raw
 from .tracklet_runner import TrackletRunner, tracking_modes
 
 # ptt_crop_scan_f32 from this many points per scan on (scan_crop=None). Measured by scripts/online_tracker_timing.py
@@ -125,6 +127,10 @@ class OnlineTracker(object):
         self.add_jobs_np = self.add_jobs_host.numpy().view(ops.CROP_JOB)
         self.scan_ws = ops._ws(ops.crop_scan_workspace(2 * S, self.scan_capacity), dev)
         self.est_buf = np.zeros((S, 5), np.float32)
+        # step_raw: the staging buffer of a host scan's interleaved rows (made at the first call) and its one-job ingest table
+        self._raw_stage = None
+        self._raw_job_host = torch.zeros(ops.SCAN_JOB.itemsize, dtype=torch.uint8).pin_memory()
+        self._raw_job_np = self._raw_job_host.numpy().view(ops.SCAN_JOB)
         self.reset()
 
     # ------------------------------------------------------------------ state
@@ -203,8 +209,45 @@ class OnlineTracker(object):
         -> {id: (center, wlh, quat, score or None)} for every live target. ValueError (bad scan, N > scan_capacity, unknown id
         in drop, id already live, more adds than free slots) leaves the state unchanged. The scan may be reused by the caller
         as soon as the call returns."""
-        core, S, dev = self.core, self.S, self.device
         t, n = self._check_scan(scan)
+        return self._step(n, add, drop, lambda cur: self.scans[cur, :, :n].copy_(t, non_blocking=True))
+
+    def step_raw(self, raw, steps=None, add=None, drop=()):
+        """step() on the sensor's own buffer: raw is an (N, C) float32 scan of interleaved rows (x, y, z, then C - 3 columns that
+        are dropped; 3 <= C <= 16, N <= scan_capacity) — a C-contiguous numpy array or a contiguous torch tensor on the host
+        (pinned: an asynchronous copy) or on the device (read in place); steps: its way into the reference frame (ops.scan_steps'
+        list: ('rotate', 3x3) / ('translate', 3) / ('affine', 3x4 or 4x4), at most four). A host scan is staged into a device
+        buffer of scan_capacity * C floats (allocated at the first call, grown if C grows); one ptt_scan_ingest_f32 launch writes
+        the planar scan straight into the resident buffer step() copies into, and the rest is step()'s own code: the same
+        results as step() on the de-interleaved, transformed scan. A bad raw or bad steps raise ValueError and leave the state
+        unchanged, as step()'s refusals do."""
+        dev = self.device
+        t = check_raw(raw, dev, self.scan_capacity)
+        recs = ops.scan_steps(steps)
+        n, C = int(t.shape[0]), int(t.shape[1])
+        if not t.is_cuda and (self._raw_stage is None or self._raw_stage.numel() < self.scan_capacity * C):
+            self._raw_stage = torch.empty(self.scan_capacity * C, dtype=torch.float32, device=dev)
+        job = self._raw_job_np
+        job[0] = np.zeros((), ops.SCAN_JOB)
+        job['raw'] = t.data_ptr() if t.is_cuda else self._raw_stage.data_ptr()
+        job['out'] = self.scans.data_ptr() + self.cur * 3 * self.scan_capacity * 4
+        job['ld'], job['n_points'], job['row_floats'], job['n_steps'] = self.scan_capacity, n, C, len(recs)
+        job['steps'][0, :len(recs)] = recs
+        if n:
+            ops.scan_ingest_check(job, 1, n)
+
+        def place(cur):
+            if n:
+                if not t.is_cuda:
+                    self._raw_stage[:n * C].copy_(t.reshape(-1), non_blocking=True)
+                # the one-job table is read from pinned host memory; the step waits for the device before it returns
+                ops.scan_ingest_device(self._raw_job_host, 1, n, dev)
+        return self._step(n, add, drop, place)
+
+    def _step(self, n, add, drop, place):
+        """What step() and step_raw() share: everything but the form the scan arrives in. place(cur) enqueues, inside the device
+        context, whatever writes the n points of this scan into self.scans[cur]; it runs once nothing can raise any more."""
+        core, S, dev = self.core, self.S, self.device
         add = {} if add is None else dict(add)
         new_boxes = {i: _as_box(b) for i, b in add.items()}
         plan = self.table.plan(list(add), drop)
@@ -213,7 +256,7 @@ class OnlineTracker(object):
         cur, prev = self.cur, 1 - self.cur
         self.cur = prev
         with torch.cuda.device(dev):
-            self.scans[cur, :, :n].copy_(t, non_blocking=True)
+            place(cur)
         n_prev, self.n_prev = self.n_prev, n
         new_slots = set(s for _, s in plan[1])
         active = np.zeros(S, np.int32)

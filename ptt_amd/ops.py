@@ -852,6 +852,93 @@ def crop_scan(jobs_np, n_jobs, max_points, device, out=None):
     return jobs_dev
 
 
+# ---- raw scans -> planar clouds in the reference frame (ptt_scan_ingest_f32), and the preload crop (ptt_scan_preload_f32)
+SCAN_STEP, SCAN_JOB, PRELOAD_JOB = np.dtype(_lib.ScanStep), np.dtype(_lib.ScanJob), np.dtype(_lib.PreloadJob)
+SCAN_MAX_STEPS = _lib.PTT_SCAN_MAX_STEPS
+SCAN_ROW_FLOATS_MIN, SCAN_ROW_FLOATS_MAX = 3, 16
+_SCAN_SHAPES = {"rotate": ((3, 3),), "translate": ((3,),), "affine": ((3, 4), (4, 4))}
+
+
+def scan_steps(steps):
+    """[('rotate', 3x3), ('translate', 3), ('affine', 3x4 or 4x4: the top three rows), ...] -> a SCAN_STEP array of that length
+    (what a SCAN_JOB's steps[:n_steps] holds); None or () -> no step. ValueError for more than SCAN_MAX_STEPS steps, an
+    unknown kind, a wrong shape or a value that is not finite."""
+    if steps is not None and not isinstance(steps, (list, tuple)):
+        raise ValueError("scan_steps: a list of (kind, matrix) pairs is expected, got %s" % type(steps).__name__)
+    steps = [] if steps is None else list(steps)
+    if len(steps) > SCAN_MAX_STEPS:
+        raise ValueError("scan_steps: %d steps, at most %d" % (len(steps), SCAN_MAX_STEPS))
+    out = np.zeros(len(steps), SCAN_STEP)
+    for k, step in enumerate(steps):
+        if not isinstance(step, (tuple, list)) or len(step) != 2 or step[0] not in _SCAN_SHAPES:
+            raise ValueError("scan_steps: step %d must be ('rotate' | 'translate' | 'affine', matrix), got %r" % (k, step))
+        kind, m = step
+        try:
+            m = np.asarray(m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else m, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("scan_steps: step %d (%s) does not hold numbers" % (k, kind))
+        if m.shape not in _SCAN_SHAPES[kind] or not np.isfinite(m).all():
+            raise ValueError("scan_steps: step %d (%s) takes a finite array of shape %s, got %s"
+                             % (k, kind, " or ".join(map(str, _SCAN_SHAPES[kind])), m.shape))
+        flat = m[:3].reshape(-1)
+        out['kind'][k] = _lib.SCAN_KINDS[kind]
+        out['m'][k, :flat.size] = flat
+    return out
+
+
+def scan_ingest_check(jobs_np, n_jobs, max_points):
+    """What ptt_scan_ingest_f32 cannot report from the device, checked on the HOST table (SCAN_JOB array): ValueError for
+    row_floats outside 3..16, n_steps outside 0..SCAN_MAX_STEPS, an unknown kind among a job's steps, n_points outside
+    0..max_points, ld < n_points."""
+    jobs = jobs_np[:int(n_jobs)]
+    if len(jobs) != int(n_jobs) or int(n_jobs) < 1 or int(max_points) < 1:
+        raise ValueError("scan_ingest: the table holds %d jobs, n_jobs=%d, max_points=%d" % (len(jobs_np), n_jobs, max_points))
+    if int(jobs['row_floats'].min()) < SCAN_ROW_FLOATS_MIN or int(jobs['row_floats'].max()) > SCAN_ROW_FLOATS_MAX:
+        raise ValueError("scan_ingest: row_floats must lie in %d..%d, got %d..%d"
+                         % (SCAN_ROW_FLOATS_MIN, SCAN_ROW_FLOATS_MAX, jobs['row_floats'].min(), jobs['row_floats'].max()))
+    if int(jobs['n_steps'].min()) < 0 or int(jobs['n_steps'].max()) > SCAN_MAX_STEPS:
+        raise ValueError("scan_ingest: n_steps must lie in 0..%d, got %d..%d" % (SCAN_MAX_STEPS, jobs['n_steps'].min(), jobs['n_steps'].max()))
+    used = np.arange(SCAN_MAX_STEPS)[None, :] < jobs['n_steps'][:, None]
+    kinds = jobs['steps']['kind']
+    if np.any(used & ~np.isin(kinds, list(_lib.SCAN_KINDS.values()))):
+        raise ValueError("scan_ingest: unknown step kind %d" % kinds[used & ~np.isin(kinds, list(_lib.SCAN_KINDS.values()))][0])
+    if int(jobs['n_points'].max()) > int(max_points) or int(jobs['n_points'].min()) < 0:
+        raise ValueError("scan_ingest: n_points must lie in 0..max_points=%d, got %d..%d" % (max_points, jobs['n_points'].min(), jobs['n_points'].max()))
+    if np.any(jobs['ld'] < jobs['n_points']):
+        raise ValueError("scan_ingest: ld < n_points (the planar rows would overlap)")
+
+
+def scan_ingest_device(jobs, n_jobs, max_points, device=None):
+    """ptt_scan_ingest_f32 over a table that was checked on the host (scan_ingest_check): `jobs` a uint8 tensor on the device, or
+    in pinned host memory (then `device` says where to launch)."""
+    device = jobs.device if device is None else torch.device(device)
+    _launch("ptt_scan_ingest_f32", device, _ptr(jobs), int(n_jobs), int(max_points), timed='ptt_scan_ingest_f32')
+
+
+def scan_ingest(jobs_np, n_jobs, max_points, device):
+    """ptt_scan_ingest_f32: raw (n, row_floats) scans -> planar (3, n) clouds through each job's steps. jobs_np: the HOST table
+    (SCAN_JOB array); it is checked (scan_ingest_check), uploaded and launched. -> the device table."""
+    scan_ingest_check(jobs_np, n_jobs, max_points)
+    with torch.cuda.device(device):
+        jobs_dev = upload_jobs(jobs_np)
+    scan_ingest_device(jobs_dev, n_jobs, max_points)
+    return jobs_dev
+
+
+def scan_preload_workspace(n_jobs, max_points):
+    """ptt_scan_preload_workspace: bytes of workspace ptt_scan_preload_f32 needs for this launch."""
+    return int(_host("ptt_scan_preload_workspace", int(n_jobs), int(max_points)))
+
+
+def scan_preload_device(jobs_dev, n_jobs, max_points, ws=None):
+    """ptt_scan_preload_f32 over a device-resident table of PRELOAD_JOB records (uint8 tensor). ws: a device buffer of at least
+    scan_preload_workspace(n_jobs, max_points) bytes (default: a fresh one)."""
+    if ws is None:
+        ws = _ws(scan_preload_workspace(n_jobs, max_points), jobs_dev.device)
+    _launch("ptt_scan_preload_f32", jobs_dev.device, _ptr(jobs_dev), int(n_jobs), int(max_points), _ptr(ws), ws.numel() * ws.element_size(),
+            timed='ptt_scan_preload_f32')
+
+
 def crop_regularize_pinned(crop_jobs_pinned, reg_jobs_dev, n_jobs, draws):
     """ptt_crop_regularize_f32: crop job w then resampling job w per workgroup, the crop table read from pinned host memory."""
     _launch("ptt_crop_regularize_f32", reg_jobs_dev.device, ctypes.c_void_p(crop_jobs_pinned.data_ptr()), _ptr(reg_jobs_dev), int(n_jobs),

@@ -303,12 +303,22 @@ class TrainBatchFeeder(TrainBatchPlan):
 
     # ------------------------------------------------------------------ resident data
     def _upload(self, tracklets):
-        """One upload per tracklet: its frames side by side in a (3, sum N_i) buffer (as TrackletRunner._load packs them)."""
+        """One upload per tracklet: its frames side by side in a (3, sum N_i) buffer (as TrackletRunner._load packs them). A
+        tracklet whose clouds are all float32 tensors on this device with adjacent points (SceneStore's views) is used in place:
+        pointer and row stride come from the tensor, which is kept alive here — the same bytes, so the same batches."""
         dev = self.device
         self.packed = []
         ptr, ld = [], []
+        here = dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())      # what a tensor's .device says
         for clouds, _ in tracklets:
             if not clouds:
+                continue
+            if all(isinstance(c, torch.Tensor) and c.device == here and c.dtype == torch.float32 and c.dim() == 2 and c.shape[0] >= 3
+                   and c.stride(1) == 1 for c in clouds):
+                for c in clouds:
+                    self.packed.append(c)
+                    ptr.append(c.data_ptr())
+                    ld.append(c.stride(0))
                 continue
             arrs = [np.ascontiguousarray((c.cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c))[0:3], np.float32) for c in clouds]
             sizes = [a.shape[1] for a in arrs]
