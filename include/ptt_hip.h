@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 34
+#define PTT_ABI_VERSION 35
 
 enum {
     PTT_OK = 0,
@@ -743,6 +743,21 @@ typedef struct ptt_train_batch_desc {
 } ptt_train_batch_desc;
 
 int ptt_train_batch_f32(const ptt_train_cand* cands_device, const ptt_train_batch_desc* desc_host, ptt_stream_t stream);
+
+/* (ABI 35) The same batch with the sample's DATA_AUGMENTOR applied (ptt/datasets/augmentor: random_world_flip, _rotation and
+ * _scaling in any order compose to one map). aug_device: n_cand records in DEVICE memory, parallel to the candidate table. The
+ * workgroup of slot b reads the record of its SOURCE candidate and stores, for every row (x, y, z) of search_points and
+ * template_points,  x' = m[0] x + m[1] y,  y' = m[2] x + m[3] y,  z' = kz z  in float32. Labels, indices, src_out, info and
+ * totals are as without it; reg_label arrives augmented from the host, as it arrives at all; a slot without a source stays all
+ * zeros. aug_device == NULL is ptt_train_batch_f32 (which forwards here). Same argument checks. */
+typedef struct ptt_train_aug {
+    float m[4];                 /* m00, m01, m10, m11 */
+    float kz;
+    float reserved[3];          /* 0 */
+} ptt_train_aug;
+
+int ptt_train_batch_aug_f32(const ptt_train_cand* cands_device, const ptt_train_aug* aug_device, const ptt_train_batch_desc* desc_host,
+                            ptt_stream_t stream);
 /* The generator of the resampling on the host (HOST pointers, no device work), for tests and tools: out4[0..3] =
  * Philox4x32-10(counter4, key2). */
 int ptt_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);

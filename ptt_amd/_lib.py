@@ -133,6 +133,12 @@ class TrainCand(Structure):
                 ("reg", c_float * 4), ("index", c_uint32), ("epoch", c_uint32), ("capacity", c_int32), ("reserved", c_int32)]
 
 
+class TrainAug(Structure):
+    """ptt_train_aug: one candidate's augmentation map, x' = m00 x + m01 y, y' = m10 x + m11 y, z' = kz z; arrays of these are
+    uploaded to the device, parallel to the candidates."""
+    _fields_ = [("m", c_float * 4), ("kz", c_float), ("reserved", c_float * 3)]
+
+
 class TrainBatchDesc(Structure):
     """ptt_train_batch_desc: the outputs and sizes of ptt_train_batch_f32 (passed by value, host memory)."""
     _fields_ = [("search_points", c_void_p), ("template_points", c_void_p), ("cls_label", c_void_p), ("reg_label", c_void_p),

@@ -567,8 +567,10 @@ __host__ __device__ __forceinline__ void philox4x32_10(const uint32_t (&ctr)[4],
 // Rows i = 4t .. 4t + 3 of one output cloud (thread-owned: one Philox block): row idx of seg0 (n0 rows) || seg1, optionally
 // the label of that row as float32, optionally the index. n == size passes the rows through in order (index -1); n == 0 (an
 // all-invalid batch) writes zeros. `vec`: size % 4 == 0 and 16-byte aligned outputs, so the 12 floats of the four rows are three
-// aligned float4 stores; otherwise element by element.
-__device__ __forceinline__ void resample_rows(bool vec, int t, int size, int n, int n0, const float* __restrict__ seg0, const float* __restrict__ seg1,
+// aligned float4 stores; otherwise element by element. AUG: every row goes through the sample's augmentation map (ptt_train_aug)
+// on its way from the registers to the store; without it the instantiation carries no such arithmetic.
+template <bool AUG>
+__device__ __forceinline__ void resample_rows(const ptt_train_aug& A, bool vec, int t, int size, int n, int n0, const float* __restrict__ seg0, const float* __restrict__ seg1,
                                               const uint8_t* __restrict__ label, uint32_t index, uint32_t which, uint32_t epoch, uint32_t k0,
                                               uint32_t k1, float* __restrict__ out, float* __restrict__ label_out, int32_t* __restrict__ idx_out) {
     const uint32_t ctr[4] = {(uint32_t)t, index, which, epoch};
@@ -588,6 +590,15 @@ __device__ __forceinline__ void resample_rows(bool vec, int t, int size, int n, 
             const float* p = src < n0 ? seg0 + (size_t)src * 3 : seg1 + (size_t)(src - n0) * 3;
             v[3 * k] = p[0]; v[3 * k + 1] = p[1]; v[3 * k + 2] = p[2];
             if (label) lab[k] = label[src] ? 1.f : 0.f;
+        }
+    }
+    if (AUG) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float x = v[3 * k], y = v[3 * k + 1];
+            v[3 * k] = A.m[0] * x + A.m[1] * y;
+            v[3 * k + 1] = A.m[2] * x + A.m[3] * y;
+            v[3 * k + 2] = A.kz * v[3 * k + 2];
         }
     }
     const int i0 = 4 * t;
@@ -610,8 +621,9 @@ __device__ __forceinline__ void resample_rows(bool vec, int t, int size, int n, 
     }
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void train_batch_kernel(const ptt_train_cand* __restrict__ cands, const ptt_train_batch_desc D) {
+template <int T, bool AUG>
+__global__ __launch_bounds__(T) void train_batch_kernel(const ptt_train_cand* __restrict__ cands, const ptt_train_aug* __restrict__ aug,
+                                                        const ptt_train_batch_desc D) {
     __shared__ int wsum[T / 64];
     __shared__ int vrank[PTT_TRAIN_MAX_CANDS + 1];          // valid candidates before c; [n_cand] = their total
     __shared__ unsigned char vflag[PTT_TRAIN_MAX_CANDS];
@@ -665,6 +677,10 @@ __global__ __launch_bounds__(T) void train_batch_kernel(const ptt_train_cand* __
         ps = c.search; pl = c.label; p1 = c.first; p2 = c.prev; index = c.index; epoch = c.epoch;
         if (threadIdx.x < 4) reg = c.reg[threadIdx.x];
     }
+    // the source's map, read once at a workgroup-uniform address (0 <= src < n_cand, the table's length); a slot without a
+    // source holds zeros and takes none
+    ptt_train_aug A = {{1.f, 0.f, 0.f, 1.f}, 1.f, {0.f, 0.f, 0.f}};
+    if (AUG && src >= 0) A = aug[__builtin_amdgcn_readfirstlane(src)];
     if (threadIdx.x < 4) D.reg_label[(size_t)b * 4 + threadIdx.x] = reg;
     if (threadIdx.x == 0) D.src_out[b] = src;
     const int S = D.search_size, Tn = D.template_size;
@@ -673,10 +689,10 @@ __global__ __launch_bounds__(T) void train_batch_kernel(const ptt_train_cand* __
     const bool vec_s = (S & 3) == 0 && !misaligned(D.search_points) && !misaligned(D.cls_label) && !misaligned(D.idx_search_out);
     const bool vec_t = (Tn & 3) == 0 && !misaligned(D.template_points) && !misaligned(D.idx_template_out);
     for (int t = threadIdx.x; 4 * t < S; t += T)
-        resample_rows(vec_s, t, S, ns, ns, ps, ps, pl, index, 0u, epoch, D.seed_lo, D.seed_hi, D.search_points + (size_t)b * S * 3,
+        resample_rows<AUG>(A, vec_s, t, S, ns, ns, ps, ps, pl, index, 0u, epoch, D.seed_lo, D.seed_hi, D.search_points + (size_t)b * S * 3,
                       D.cls_label + (size_t)b * S, D.idx_search_out ? D.idx_search_out + (size_t)b * S : nullptr);
     for (int t = threadIdx.x; 4 * t < Tn; t += T)
-        resample_rows(vec_t, t, Tn, n1 + n2, n1, p1, p2, nullptr, index, 1u, epoch, D.seed_lo, D.seed_hi, D.template_points + (size_t)b * Tn * 3,
+        resample_rows<AUG>(A, vec_t, t, Tn, n1 + n2, n1, p1, p2, nullptr, index, 1u, epoch, D.seed_lo, D.seed_hi, D.template_points + (size_t)b * Tn * 3,
                       nullptr, D.idx_template_out ? D.idx_template_out + (size_t)b * Tn : nullptr);
 }
 
@@ -972,16 +988,31 @@ extern "C" int ptt_track_select_update(const float* proposals, int P, const int3
 }
 
 
-extern "C" int ptt_train_batch_f32(const ptt_train_cand* cands_device, const ptt_train_batch_desc* desc_host, ptt_stream_t stream) {
-    if (!cands_device || !desc_host) return fail(PTT_EINVAL, "ptt_train_batch_f32: null pointer");
+// Both entry points of the training batch: `who` names the one that was called, in its errors and in the launch check.
+static int train_batch_launch(const char* who, const ptt_train_cand* cands_device, const ptt_train_aug* aug_device,
+                              const ptt_train_batch_desc* desc_host, ptt_stream_t stream) {
+    if (!cands_device || !desc_host) return fail(PTT_EINVAL, "%s: null pointer", who);
     const ptt_train_batch_desc D = *desc_host;
     if (D.B < 1 || D.n_cand < D.B || D.n_cand > PTT_TRAIN_MAX_CANDS || D.search_size < 1 || D.template_size < 1 || D.min_points < 2)
-        return fail(PTT_EINVAL, "ptt_train_batch_f32: B=%d n_cand=%d (B..%d) search_size=%d template_size=%d min_points=%d (>= 2)", D.B, D.n_cand,
+        return fail(PTT_EINVAL, "%s: B=%d n_cand=%d (B..%d) search_size=%d template_size=%d min_points=%d (>= 2)", who, D.B, D.n_cand,
                     PTT_TRAIN_MAX_CANDS, D.search_size, D.template_size, D.min_points);
     if (!D.search_points || !D.template_points || !D.cls_label || !D.reg_label || !D.src_out)
-        return fail(PTT_EINVAL, "ptt_train_batch_f32: null output");
-    hipLaunchKernelGGL((train_batch_kernel<256>), dim3(D.B), dim3(256), 0, as_stream(stream), cands_device, D);
+        return fail(PTT_EINVAL, "%s: null output", who);
+    if (aug_device) {
+        hipLaunchKernelGGL((train_batch_kernel<256, true>), dim3(D.B), dim3(256), 0, as_stream(stream), cands_device, aug_device, D);
+        return check_launch("train_batch_kernel<AUG>");
+    }
+    hipLaunchKernelGGL((train_batch_kernel<256, false>), dim3(D.B), dim3(256), 0, as_stream(stream), cands_device, aug_device, D);
     return check_launch("train_batch_kernel");
+}
+
+extern "C" int ptt_train_batch_f32(const ptt_train_cand* cands_device, const ptt_train_batch_desc* desc_host, ptt_stream_t stream) {
+    return train_batch_launch("ptt_train_batch_f32", cands_device, nullptr, desc_host, stream);
+}
+
+extern "C" int ptt_train_batch_aug_f32(const ptt_train_cand* cands_device, const ptt_train_aug* aug_device, const ptt_train_batch_desc* desc_host,
+                                       ptt_stream_t stream) {
+    return train_batch_launch("ptt_train_batch_aug_f32", cands_device, aug_device, desc_host, stream);
 }
 
 extern "C" int ptt_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4) {

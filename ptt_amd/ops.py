@@ -990,14 +990,21 @@ def box_overlap(gt, pred, ref_coord, dims=3, out=None):
 
 # --------------------------------------------------------------------------- N5: device-resident training batches
 TRAIN_CAND, TRAIN_BATCH_DESC = np.dtype(_lib.TrainCand), np.dtype(_lib.TrainBatchDesc)
+TRAIN_AUG = np.dtype(_lib.TrainAug)
 TRAIN_MAX_CANDS = _lib.PTT_TRAIN_MAX_CANDS
 
 
-def train_batch(cands_dev, desc, device):
-    """ptt_train_batch_f32: one training batch out of the crops of its candidates — `cands_dev` a device-resident table of
+def train_batch(cands_dev, desc, device, aug_dev=None):
+    """ptt_train_batch_aug_f32: one training batch out of the crops of its candidates — `cands_dev` a device-resident table of
     ptt_train_cand records (uint8 tensor, or a view into a larger table), `desc` a one-element TRAIN_BATCH_DESC array (host memory,
-    read before this returns). Enqueued on the current stream, behind the crop launch that fills the candidates' scratch."""
-    _launch("ptt_train_batch_f32", device, _ptr(cands_dev), ctypes.c_void_p(desc.ctypes.data), timed='ptt_train_batch_f32')
+    read before this returns), `aug_dev` a device-resident table of one TRAIN_AUG record per candidate, or None for samples as
+    they are, which goes through ptt_train_batch_f32 (each entry point under its own name in errors and in kernel timing).
+    Enqueued on the current stream, behind the crop launch that fills the candidates' scratch."""
+    if aug_dev is None:
+        _launch("ptt_train_batch_f32", device, _ptr(cands_dev), ctypes.c_void_p(desc.ctypes.data), timed='ptt_train_batch_f32')
+    else:
+        _launch("ptt_train_batch_aug_f32", device, _ptr(cands_dev), _ptr(aug_dev), ctypes.c_void_p(desc.ctypes.data),
+                timed='ptt_train_batch_aug_f32')
 
 
 def philox4x32_10(counter, key):

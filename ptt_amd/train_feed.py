@@ -26,6 +26,12 @@ generator (per worker process, order-dependent):
 A rejected sample is replaced as the reference replaces it, by a uniformly random dataset index — drawn ahead of time: every
 batch carries `spare` extra candidates (np.random.RandomState([seed, e, batch number]).randint(0, len, spare)), and the kernel
 hands the r-th rejected primary the r-th valid spare.
+
+DATA_AUGMENTOR (`augmentor=`, what ptt.datasets.augmentor.DataAugmentor takes): the queue of random_world_flip / _rotation /
+_scaling of a sample is one map [x'; y'] = M [x; y], z' = kz z. The host draws it per candidate from a generator of its own,
+RandomState([seed, e, j, 0x415547]) — so turning the augmentor on moves no offset, index or crop — forms M, kz and the augmented
+reg_label in float64, and ships five float32 per candidate in a ptt_train_aug table behind the candidates (the same upload);
+ptt_train_batch_aug_f32 applies the map to the rows it has just gathered, right before it stores them.
 """
 import warnings
 
@@ -33,10 +39,12 @@ import numpy as np
 import torch
 
 from . import ops
+from .datasets.augmentor import DataAugmentor, augmentor_utils
 from .datasets.kitti import box_math as bm
 from .tracklet_shard import dist_info, shard_indices
 
 _MVN = None
+AUG_STREAM = 0x415547         # 'AUG': the last seed word of a candidate's augmentation generator
 
 
 def _search_normal(rs):
@@ -107,7 +115,7 @@ class TrainBatchPlan(object):
 
     def __init__(self, tracklets, batch_size=48, search_size=1024, template_size=512, search_offset=0.0, search_scale=1.25,
                  model_offset=0.0, model_scale=1.25, use_z=True, refine_box=True, candidates_per_frame=4, sampled_interval=1,
-                 min_points=20, spare=None, seed=0, shuffle=True, drop_last=True, rank=None, world=None):
+                 min_points=20, spare=None, seed=0, shuffle=True, drop_last=True, rank=None, world=None, augmentor=None):
         self.B, self.S, self.T = int(batch_size), int(search_size), int(template_size)
         self.spare = max(4, self.B // 8) if spare is None else int(spare)
         self.C = self.B + self.spare
@@ -129,6 +137,7 @@ class TrainBatchPlan(object):
         self.rank, self.world = int(rank), int(world)
         self.epoch = 0
         self._orders = {}
+        self._augment(augmentor)
         self._tables(tracklets)
         self.length = dataset_length(self.n_frames, self.cpf, self.interval)
         if self.length < 1:
@@ -145,7 +154,7 @@ class TrainBatchPlan(object):
                     search_offset=get('SEARCH_BB_OFFSET', 0.0), search_scale=get('SEARCH_BB_SCALE', 1.25),
                     model_offset=get('MODEL_BB_OFFSET', 0.0), model_scale=get('MODEL_BB_SCALE', 1.25), use_z=get('USE_Z_AXIS', True),
                     refine_box=get('REFINE_BOX_SIZE', True), candidates_per_frame=get('NUM_CANDIDATES_PERFRAME', 4),
-                    sampled_interval=get('SAMPLED_INTERVAL', 1))
+                    sampled_interval=get('SAMPLED_INTERVAL', 1), augmentor=get('DATA_AUGMENTOR', None))
 
     @classmethod
     def from_config(cls, tracklets, data_cfg, batch_size, **kw):
@@ -195,7 +204,8 @@ class TrainBatchPlan(object):
         """The host-side description of batch `batch` of epoch `epoch`: dict of
              index (C,)  the dataset indices, B primaries then the spares;   anno, aug, tracklet, frame (C,)  what they address;
              search_offset, template_offset (C,3)  the offsets as used (after get_box_by_offset's redraws);   reg_label (C,4) float64
-        plus, for the launch, the frames and the boxes' crop quantities (`_frames`, `_jobs`)."""
+        plus, for the launch, the frames and the boxes' crop quantities (`_frames`, `_jobs`). With an augmentor also aug_map (C,5)
+        float32, aug_draws (C, len(aug_kinds)), aug_kinds and reg_label_raw; reg_label is then the augmented one (_augmentation)."""
         epoch, batch = int(epoch), int(batch)
         if not 0 <= batch < self.n_batches:
             raise IndexError("batch %d of %d" % (batch, self.n_batches))
@@ -244,9 +254,66 @@ class TrainBatchPlan(object):
         # reg_label (:321-325): the ground-truth centre carried through the sample box's translate / rotate, and -theta
         R2 = bm.q_rotation_matrix(bm.q_from_matrix(jobs['rot'][:, 0].reshape(C, 3, 3)))
         reg = np.concatenate([np.einsum('...ij,...j->...i', R2, gc + jobs['trans'][:, 0]), -off_s[:, 2:3]], 1)
-        return {'index': index, 'anno': anno, 'aug': aug, 'tracklet': self.tracklet_of[anno], 'frame': self.frame_of[anno],
-                'search_offset': off_s, 'template_offset': off_t, 'reg_label': reg,
-                '_frames': (anno, first, prev), '_jobs': jobs}
+        out = {'index': index, 'anno': anno, 'aug': aug, 'tracklet': self.tracklet_of[anno], 'frame': self.frame_of[anno],
+               'search_offset': off_s, 'template_offset': off_t, 'reg_label': reg,
+               '_frames': (anno, first, prev), '_jobs': jobs}
+        if self.aug_steps is not None:
+            out['reg_label_raw'], out['aug_kinds'] = reg, self.aug_kinds
+            out['aug_map'], out['reg_label'], out['aug_draws'] = self._augmentation(epoch, index, reg)
+        return out
+
+    def _augment(self, augmentor):
+        """The DATA_AUGMENTOR queue as the flat list of its draws, `aug_steps` = [(kind, range)] with kind flip_x / flip_y /
+        rotation / scaling (`aug_kinds`: the kinds alone, the columns of plan()['aug_draws']); None without an augmentor. A
+        scaling whose range is a no-op draws nothing and is left out. Unknown NAMEs and axes raise here (DataAugmentor's checks)."""
+        self.aug_steps, self.aug_kinds = None, ()
+        if augmentor is None:
+            return
+        if not isinstance(augmentor, DataAugmentor):
+            augmentor = DataAugmentor(None, augmentor, None)
+        steps = []
+        for name, arg in augmentor.steps:
+            if name == 'random_world_flip':
+                steps += [('flip_' + axis, None) for axis in arg]
+            elif name == 'random_world_rotation':
+                steps.append(('rotation', arg))
+            elif not augmentor_utils.scaling_is_noop(arg):
+                steps.append(('scaling', arg))
+        self.aug_steps, self.aug_kinds = steps, tuple(kind for kind, _ in steps)
+
+    def _augmentation(self, epoch, index, reg):
+        """DataAugmentor.forward of every candidate as ONE map: whatever the queue, the points go through [x'; y'] = M [x; y],
+        z' = kz z. -> (aug_map (C,5) float32 = m00, m01, m10, m11, kz; the augmented reg_label (C,4) float64; the draws (C, len(
+        aug_kinds)) float64, flags as 0 / 1). The draws of dataset index j come from RandomState([seed, epoch, j, AUG_STREAM]) in
+        queue order, through augmentor_utils' own calls; M, kz and the label's centre are formed in float64, with the cos / sin
+        of the angle as float32 holds it (the angle the reference's rotation uses); theta follows the operations one by one."""
+        C, steps = len(index), self.aug_steps
+        amap, out, draws = np.zeros((C, 5)), np.array(reg, np.float64), np.zeros((C, len(steps)))
+        rs = np.random.RandomState(0)
+        for c in range(C):
+            rs.seed(_host_seed(self.seed, epoch, index[c]) + [AUG_STREAM])
+            M, kz, theta = np.eye(2), 1.0, reg[c, 3]
+            for k, (kind, span) in enumerate(steps):
+                if kind == 'flip_x':                                   # negates y
+                    d = augmentor_utils.draw_flag(rs)
+                    if d:
+                        M[1], theta = -M[1], -theta
+                elif kind == 'flip_y':                                 # negates x
+                    d = augmentor_utils.draw_flag(rs)
+                    if d:
+                        M[0], theta = -M[0], -(theta + np.pi)
+                elif kind == 'rotation':
+                    d = augmentor_utils.draw_uniform(rs, span)
+                    a = np.float64(np.float32(d))
+                    M = np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]).dot(M)
+                    theta = theta + d
+                else:
+                    d = augmentor_utils.draw_uniform(rs, span)
+                    M, kz = M * d, kz * d
+                draws[c, k] = d
+            amap[c, 0:4], amap[c, 4] = M.reshape(4), kz
+            out[c, 0:2], out[c, 2], out[c, 3] = M.dot(reg[c, 0:2]), kz * reg[c, 2], theta
+        return (amap + 0.0).astype(np.float32), out, draws
 
 
 
@@ -260,7 +327,9 @@ class TrainBatchFeeder(TrainBatchPlan):
     fewer rejects the sample (the reference's 20). spare: replacement candidates per batch, default max(4, batch_size // 8).
     seed: a non-negative integer below 2^64. shuffle: the epoch's order is RandomState([seed, epoch]).permutation(len), else the
     identity; it is dealt to the ranks as tracklet_shard.shard_indices deals tracklets (rank / world default to the process
-    group). drop_last=False fills the last batch by wrapping to the rank's first indices.
+    group). drop_last=False fills the last batch by wrapping to the rank's first indices. augmentor: a DATA_AUGMENTOR section (a
+    list of entries, a mapping with AUG_CONFIG_LIST, or a DataAugmentor), applied to search_points, template_points and reg_label
+    of every sample (module text); from_config reads the key when the config has it.
 
     len(feeder) = batches per epoch for this rank; set_epoch(e) selects the epoch; iterating yields dicts with the keys, shapes
     and dtypes of train_step.synthetic_train_batch. plan(epoch, batch) describes a batch on the host alone. stats() reads the
@@ -280,12 +349,14 @@ class TrainBatchFeeder(TrainBatchPlan):
 
     def __init__(self, tracklets, device, batch_size=48, search_size=1024, template_size=512, search_offset=0.0, search_scale=1.25,
                  model_offset=0.0, model_scale=1.25, use_z=True, refine_box=True, candidates_per_frame=4, sampled_interval=1,
-                 min_points=20, spare=None, seed=0, shuffle=True, drop_last=True, rank=None, world=None, depth=2, stream=None):
+                 min_points=20, spare=None, seed=0, shuffle=True, drop_last=True, rank=None, world=None, depth=2, stream=None,
+                 augmentor=None):
         self.device = dev = torch.device(device)
         if dev.type != 'cuda':
             raise RuntimeError("TrainBatchFeeder runs on the HIP device (there is no CPU fallback)")
         TrainBatchPlan.__init__(self, tracklets, batch_size, search_size, template_size, search_offset, search_scale, model_offset, model_scale,
-                                use_z, refine_box, candidates_per_frame, sampled_interval, min_points, spare, seed, shuffle, drop_last, rank, world)
+                                use_z, refine_box, candidates_per_frame, sampled_interval, min_points, spare, seed, shuffle, drop_last, rank, world,
+                                augmentor)
         self.depth = max(1, int(depth))
         # one producer stream for the feeder's whole life: the scratch, the device table and the counters are shared by all batches
         # and ordered by that stream alone
@@ -338,9 +409,11 @@ class TrainBatchFeeder(TrainBatchPlan):
         self.counts = torch.zeros((C, 3), dtype=torch.int32, device=dev)
         self.totals = torch.zeros(4, dtype=torch.int64, device=dev)
         self.jobs_bytes = 3 * C * ops.CROP_JOB.itemsize
-        nbytes = self.jobs_bytes + C * ops.TRAIN_CAND.itemsize
+        aug_at = self.jobs_bytes + C * ops.TRAIN_CAND.itemsize        # the augmentation records ride at the end of the same table
+        nbytes = aug_at + (C * ops.TRAIN_AUG.itemsize if self.aug_steps is not None else 0)
         self.table_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.cands_dev = self.table_dev[self.jobs_bytes:]
+        self.aug_dev = self.table_dev[aug_at:] if self.aug_steps is not None else None
         out_ptr = (self.crop_out.data_ptr() + (np.arange(C)[:, None] * 3 + np.arange(3)[None]) * (cap * 12)).astype(np.uint64)
         cnt_ptr = (self.counts.data_ptr() + (np.arange(C)[:, None] * 3 + np.arange(3)[None]) * 4).astype(np.uint64)
         lab_ptr = (self.labels.data_ptr() + np.arange(C) * cap).astype(np.uint64)
@@ -349,12 +422,13 @@ class TrainBatchFeeder(TrainBatchPlan):
             pinned = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
             host = pinned.numpy()
             jobs = host[:self.jobs_bytes].view(ops.CROP_JOB).reshape(C, 3)
-            cands = host[self.jobs_bytes:].view(ops.TRAIN_CAND)
+            cands = host[self.jobs_bytes:aug_at].view(ops.TRAIN_CAND)
+            augs = host[aug_at:].view(ops.TRAIN_AUG) if self.aug_steps is not None else None
             jobs['out'], jobs['count'], jobs['capacity'] = out_ptr, cnt_ptr, cap
             jobs['label_out'][:, 0] = lab_ptr
             cands['search'], cands['first'], cands['prev'] = out_ptr[:, 0], out_ptr[:, 1], out_ptr[:, 2]
             cands['label'], cands['counts'], cands['capacity'] = lab_ptr, cnt_ptr[:, 0], cap
-            self._staging.append({'pinned': pinned, 'jobs': jobs, 'cands': cands, 'uploaded': torch.cuda.Event(), 'used': False})
+            self._staging.append({'pinned': pinned, 'jobs': jobs, 'cands': cands, 'augs': augs, 'uploaded': torch.cuda.Event(), 'used': False})
         self._sets = [_OutputSet(self, dev) for _ in range(self.depth)]
         self._marks = [torch.cuda.Event() for _ in range(self.depth)]
         self.last = None                                      # the _OutputSet of the latest batch: src, idx_search, idx_template, info
@@ -372,6 +446,8 @@ class TrainBatchFeeder(TrainBatchPlan):
         col['ltrans'], col['lrot'], col['llo'], col['lhi'] = src['trans'][:, 3], src['rot'][:, 3], src['lo2'][:, 3], src['hi2'][:, 3]
         cands['reg'] = plan['reg_label'].astype(np.float32)
         cands['index'], cands['epoch'] = plan['index'].astype(np.uint32), np.uint32(epoch & 0xffffffff)
+        if st['augs'] is not None:
+            st['augs']['m'], st['augs']['kz'] = plan['aug_map'][:, 0:4], plan['aug_map'][:, 4]
 
     # ------------------------------------------------------------------ production
     def batch(self, epoch, batch):
@@ -398,7 +474,7 @@ class TrainBatchFeeder(TrainBatchPlan):
             st['uploaded'].record(prod)
             st['used'] = True
             ops.crop_compact(self.table_dev, 3 * self.C)
-            ops.train_batch(self.cands_dev, out.desc, dev)
+            ops.train_batch(self.cands_dev, out.desc, dev, self.aug_dev)
             if self.timing_events is not None:
                 self.timing_events[1].record(prod)
             if side:
