@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 35
+#define PTT_ABI_VERSION 36
 
 enum {
     PTT_OK = 0,
@@ -1160,6 +1160,21 @@ int ptt_optim_clip_step_dev_f32(const ptt_optim_tensor* tensors_device, const pt
                                 const int32_t* chunk_tensor_device, const int64_t* chunk_first_device, int n_chunks,
                                 const ptt_optim_hyper* hyper_device, int n_groups, float max_norm, int write_clipped, double* partial,
                                 size_t partial_elems, float* norm_out, ptt_stream_t stream);
+/* The step ledger: one launch (one workgroup, one wave) appends one row of a training step's scalars to a ring in device memory
+ * and updates running statistics — what the reference's loop reads back with loss.item() and four tb_dict values on every step
+ * (tools/train_utils/train_utils.py:54-70), without a host read. Capturable: no host reads, no allocation; ordered by the stream
+ * alone (no atomics), so it is recorded behind the optimizer's update of a captured step.
+ *   losses: the first five floats of ptt_track_losses_f32's out8 = [total, seed cls, seed reg, proposal cls, proposal reg]
+ *   norm:   the optimizer's norm_out (one float), or NULL: column 5 is then written as 0 and takes no part in the finiteness test
+ *   ring:   (capacity, PTT_LEDGER_COLS) float32; row k (counted from 0 over the ledger's life) goes to slot k % capacity, bit for bit
+ *   counts: int64[2] = {appended: rows ever appended; non_finite: rows with an inf / NaN among the provided columns}
+ *   sums:   double[PTT_LEDGER_COLS]: per column, the sum over the FINITE rows only, added in append order by one lane per column
+ *           (a host loop `s += (double)x` over those rows reproduces it bit for bit)
+ * counts and sums start from what the caller put there (zeros). PTT_EINVAL, nothing launched: losses == NULL, capacity < 1, a
+ * null ring / counts / sums. */
+#define PTT_LEDGER_COLS 6
+int ptt_step_ledger_f32(const float* losses, const float* norm, float* ring, long long capacity, int64_t* counts, double* sums,
+                        ptt_stream_t stream);
 /* The two element-wise ends of CosineSimAug's cosine map in training (p2b_xcoor.py:35-42 via nn.CosineSimilarity); the map
  * itself is a batched product of unit rows.
  *   ptt_unit_rows_f32     x addressed as x[b * sb + j * sn + c * sc] (any layout) -> unit (B,n,C) rows x / max(|x|, eps) and

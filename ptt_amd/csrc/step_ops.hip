@@ -361,9 +361,50 @@ __global__ __launch_bounds__(256) void cos_bwd_rows_kernel(const float* __restri
     for (int c = lane; c < C; c += 64) out[c * sc] = (A[p * C + c] - r * unit[p * C + c]) * inv;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The step ledger: what the reference's loop reads back with loss.item() and four tb_dict values on every step
+// (tools/train_utils/train_utils.py:54-70), kept on the device instead. One wave appends one row of PTT_LEDGER_COLS floats to a
+// ring and adds it to running float64 sums; the launch is ordered by its stream alone (it sits behind the optimizer's update in
+// the captured step), so nothing here is atomic. Lane c owns column c: it copies the value's BITS into the ring (a NaN keeps its
+// payload) and is the only lane that ever touches sum[c], in append order. Lane 0 alone reads and writes the two counters.
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void step_ledger_kernel(const float* __restrict__ losses, const float* __restrict__ norm,
+                                                         float* __restrict__ ring, long long capacity, int64_t* __restrict__ counts,
+                                                         double* __restrict__ sums) {
+    const int lane = threadIdx.x;
+    const bool col = lane < PTT_LEDGER_COLS;
+    const bool given = lane < PTT_LEDGER_COLS - 1 || (lane == PTT_LEDGER_COLS - 1 && norm != nullptr);
+    float v = 0.f;
+    if (given) v = lane < PTT_LEDGER_COLS - 1 ? losses[lane] : norm[0];
+    const bool bad = given && (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;          // inf or NaN, whatever the FP flags
+    const bool row_bad = __ballot(bad) != 0ull;
+    long long k = 0;
+    if (lane == 0) k = counts[0];
+    k = __shfl(k, 0);
+    long long slot = k % capacity;
+    if (slot < 0) slot += capacity;                          // a counter someone overwrote must still never leave the ring
+    if (col) {
+        ring[slot * PTT_LEDGER_COLS + lane] = v;
+        if (!row_bad) sums[lane] += (double)v;
+    }
+    if (lane == 0) {
+        counts[0] = k + 1;
+        if (row_bad) counts[1] += 1;
+    }
+}
+
 }  // namespace ptt
 
 using namespace ptt;
+
+extern "C" int ptt_step_ledger_f32(const float* losses, const float* norm, float* ring, long long capacity, int64_t* counts, double* sums,
+                                   ptt_stream_t stream) {
+    if (!losses) return fail(PTT_EINVAL, "ptt_step_ledger_f32: null losses");
+    if (capacity < 1) return fail(PTT_EINVAL, "ptt_step_ledger_f32: capacity=%lld", capacity);
+    if (!ring || !counts || !sums) return fail(PTT_EINVAL, "ptt_step_ledger_f32: null ring or state");
+    hipLaunchKernelGGL(step_ledger_kernel, dim3(1), dim3(64), 0, as_stream(stream), losses, norm, ring, capacity, counts, sums);
+    return check_launch("step_ledger_kernel");
+}
 
 extern "C" int ptt_track_losses_f32(const ptt_track_loss_desc* d, float* out8, float* total, ptt_stream_t stream) {
     if (int rc = loss_desc_check("ptt_track_losses_f32", d)) return rc;

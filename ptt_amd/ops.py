@@ -2291,6 +2291,26 @@ class OptimTable(_GradPointerTable):
         return self.norm
 
 
+LEDGER_COLS = _lib.DEFINES["PTT_LEDGER_COLS"]
+
+
+def step_ledger(loss_values, norm, ring, counts, sums):
+    """One row of a training step's scalars appended to a device ring (ptt_step_ledger_f32, one single-wave launch, capturable):
+    loss_values = track_losses' out (>= 5 float32: total and the four un-weighted losses), norm = the optimizer's (1,) norm tensor
+    or None (column 5 is then 0), ring (capacity, 6) float32, counts (2,) int64 = [appended, non_finite], sums (6,) float64.
+    Row k goes to slot k % capacity; the sums run over the finite rows in append order."""
+    _chk(loss_values, "loss_values", torch.float32)
+    _chk(ring, "ring", torch.float32, 2)
+    _chk(counts, "counts", torch.int64, 1)
+    _chk(sums, "sums", torch.float64, 1)
+    if norm is not None:
+        _chk(norm, "norm", torch.float32)
+    if loss_values.numel() < LEDGER_COLS - 1 or (norm is not None and norm.numel() < 1) or ring.shape[1] != LEDGER_COLS \
+            or counts.numel() != 2 or sums.numel() != LEDGER_COLS:
+        raise ValueError("step_ledger: loss_values (>= 5), norm (1,) or None, ring (capacity, %d), counts (2,), sums (%d,)" % (LEDGER_COLS, LEDGER_COLS))
+    _launch("ptt_step_ledger_f32", ring.device, _ptr(loss_values), _ptr(norm), _ptr(ring), ring.shape[0], _ptr(counts), _ptr(sums))
+
+
 def unit_rows_eps(x, eps):
     """(B,C,n) float32 in any strides -> (unit (B,n,C) = x / max(|x|, eps) over the channel axis as point-major rows,
     nrm (B,n) = max(|x|, eps), negative where the clamp is active) — ptt_unit_rows_f32."""

@@ -80,6 +80,8 @@ class _CapturedStep(object):
         self.signature = self._signature(batch)
         self.first, self.second = torch.cuda.CUDAGraph(), None
         self.loss, self.tables, self.optimizer_state, self.packs = None, None, None, None
+        self.loss_values = None           # with a ledger: the one-launch losses' (8,) buffer the recorded append reads
+        self.ledger = False               # the recorded launches end with the ledger's append
         self.bn_buffers = []              # running statistics the recorded launches update through raw pointers
 
     @staticmethod
@@ -109,7 +111,7 @@ class DataParallelTrainer(object):
     """
 
     def __init__(self, model, device, lr=1e-3, betas=(0.5, 0.999), eps=1e-6, clip=10.0, bucket_cap_mb=25, sync_bn=False, force_ddp=False,
-                 reducer=None, graph=None, graph_warmup=3, optimizer=None, scheduler=None):
+                 reducer=None, graph=None, graph_warmup=3, optimizer=None, scheduler=None, ledger=None):
         """graph: None = replay the step as hipGraphs where that is possible (HIP device, flat reducer, no SyncBatchNorm exchange;
         anything else steps eagerly), True = the same but raise where it is not possible, False = always eager. graph_warmup:
         eager steps before the capture (the plans, tables and workspaces of a step are built by them).
@@ -121,7 +123,11 @@ class DataParallelTrainer(object):
         model -> optimizer (ptt_amd.optimization.build_optimizer gives the ones of a config's OPTIMIZATION block). One without
         the capture protocol of ptt_amd.optim (a stock torch optimizer) steps eagerly after `clip_grad_norm_`.
         scheduler: an object whose .step(it) is called with the running iteration count at the top of every step(), before the
-        optimizer's host half reads lr / betas / momentum (tools/train_utils/train_utils.py:26-27)."""
+        optimizer's host half reads lr / betas / momentum (tools/train_utils/train_utils.py:26-27).
+        ledger: None = nothing changes; a ptt_amd.fit.StepLedger = every step appends one row (the five loss values of the one-launch
+        losses and the gradient norm) to it with one single-wave launch behind the optimizer's update — in the captured step a node
+        of the graph, so a per-step loss curve costs no host read. `ledger_fed` turns False (with one warning) where that is not
+        possible: a CPU device, or a tracker that took the heads' own losses."""
         self.device = torch.device(device)
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         collective = self.world > 1 or (force_ddp and dist.is_available() and dist.is_initialized())
@@ -153,7 +159,7 @@ class DataParallelTrainer(object):
         else:
             self.optimizer = optimizer(self.model)
         self.scheduler = scheduler
-        self.epoch_scheduler = None       # from_optim_cfg: a per-epoch schedule ('step'), stepped by the caller
+        self.epoch_scheduler = None       # from_optim_cfg: a per-epoch schedule ('step'), stepped by the caller's loop (ptt_amd.fit.fit)
         self.iteration = 0                # steps taken: what scheduler.step() is called with
         self._fused_clip = hasattr(self.optimizer, "prepare_graph_step")      # ptt_amd.optim: step(max_norm=...) clips
         self.clip = clip
@@ -174,6 +180,10 @@ class DataParallelTrainer(object):
         self.captured = None              # _CapturedStep once the step has been captured
         self.graph_steps = 0
         self._capture_misses = 0
+        self.ledger = ledger
+        self.ledger_fed = ledger is not None and self.device.type == 'cuda'
+        self.tb_dict = None               # the tb_dict of the last EAGER forward pass (a replay has none: None then)
+        self._loss_values = None          # with a ledger: the one-launch losses' device values of the step being run or recorded
 
     def sync_replicas(self, buffers_only=False):
         """Every parameter and buffer (BatchNorm running statistics, num_batches_tracked) takes rank 0's value — what
@@ -186,12 +196,33 @@ class DataParallelTrainer(object):
 
     def _local_forward_backward(self, batch):
         """This rank's loss and gradients, finished into the sink's flat buffer (flat reducer only)."""
-        ret, _, _ = self.model(dict(batch))
+        ret, tb_dict, _ = self.model(dict(batch))
+        self.tb_dict = tb_dict
+        self._note_loss_values(tb_dict)
         loss = ret['loss'] if ret['loss'].dim() == 0 else ret['loss'].mean()
         with self.sink.collecting():
             loss.backward()
         self.sink.flush()
         return loss
+
+    def _note_loss_values(self, tb_dict):
+        """With a ledger: the device tensor behind the tb_dict's train_ops.LossValues numbers (held here so that its memory
+        outlives the backward pass — inside a capture it is what the recorded append reads on every replay); None where the
+        tracker took the heads' own losses."""
+        if self.ledger is None:
+            return
+        owner = getattr(next(iter(tb_dict.values()), None), "owner", None) if isinstance(tb_dict, dict) else None
+        values = getattr(owner, "device_values", None)
+        self._loss_values = values if (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32) else None
+
+    def _ledger_norm(self, norm):
+        return norm.reshape(-1) if (torch.is_tensor(norm) and norm.is_cuda and norm.dtype == torch.float32 and norm.numel() == 1) else None
+
+    def _ledger_unfed(self):
+        if self.ledger_fed:
+            self.ledger_fed = False
+            warnings.warn("DataParallelTrainer: the step ledger cannot be fed (no one-launch loss values on a HIP device); "
+                          "read loss.item() per step instead")
 
     def _reduce(self):
         # the mean over ranks, as DistributedDataParallel forms it: one all-reduce of the whole gradient
@@ -200,7 +231,9 @@ class DataParallelTrainer(object):
     def forward_backward(self, batch):
         """loss.mean() and its gradients (averaged over ranks); no optimiser step."""
         if self.sink is None:
-            ret, _, _ = self.model(dict(batch))
+            ret, tb_dict, _ = self.model(dict(batch))
+            self.tb_dict = tb_dict
+            self._note_loss_values(tb_dict)
             loss = ret['loss'] if ret['loss'].dim() == 0 else ret['loss'].mean()
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
@@ -226,12 +259,20 @@ class DataParallelTrainer(object):
             if self.captured is not None and self.captured.accepts(batch):
                 return self._replay(batch)
         loss = self.forward_backward(batch)
+        norm = None
         if self._fused_clip:
             self.optimizer.step(max_norm=self.clip if self.clip else None)
+            norm = self.optimizer.last_norm if self.clip else None
         else:
             if self.clip:
-                torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
+                norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
             self.optimizer.step()
+        if self.ledger is not None:
+            if self.ledger_fed and self._loss_values is not None:
+                self.ledger.append(self._loss_values, self._ledger_norm(norm))
+            else:
+                self._ledger_unfed()
+            self._loss_values = None
         self.tracker.update_global_step()
         self.eager_steps += 1
         return loss
@@ -274,14 +315,17 @@ class DataParallelTrainer(object):
             # same — capturing is a property of the stream
             with cap.packs, torch.cuda.graph(cap.first, capture_error_mode="thread_local"):
                 cap.loss = self._local_forward_backward(cap.static)
+                cap.loss_values = self._loss_values
                 if not self._collective_cfg:
                     self.optimizer.record_graph_step(clip)
+                    self._record_ledger(cap, clip)
             if self._collective_cfg:
                 cap.second = torch.cuda.CUDAGraph()
                 with cap.packs, torch.cuda.graph(cap.second, pool=cap.first.pool(), capture_error_mode="thread_local"):
                     if self.world > 1:
                         self.sink.flat.mul_(1.0 / self.world)
                     self.optimizer.record_graph_step(clip)
+                    self._record_ledger(cap, clip)
             cap.tables = ops.finish_capture_uploads()
         except Exception as e:                                # noqa: BLE001 — whatever the runtime refuses, the eager step still works
             ops.finish_capture_uploads()
@@ -294,8 +338,15 @@ class DataParallelTrainer(object):
                           for t in (m.running_mean, m.running_var, m.num_batches_tracked) if t is not None]
         self.captured = cap
 
+    def _record_ledger(self, cap, clip):
+        """The ledger's append as a node of the graph being recorded, behind the optimizer's update (the row needs its norm)."""
+        if self.ledger is not None and self.ledger_fed and cap.loss_values is not None:
+            self.ledger.record(cap.loss_values, self._ledger_norm(self.optimizer.last_norm) if clip is not None else None)
+            cap.ledger = True
+
     def _replay(self, batch):
         cap = self.captured
+        self.tb_dict = None
         cap.load(batch)
         self.optimizer.begin_graph_step(self.clip if self.clip else None)
         cap.first.replay()
@@ -306,6 +357,11 @@ class DataParallelTrainer(object):
         self.optimizer.end_graph_step()
         # the replay moved the running statistics through raw pointers; the eval-mode parameter caches key on their versions
         _bump_versions(cap.bn_buffers)
+        if self.ledger is not None:
+            if cap.ledger:
+                self.ledger.replayed()
+            else:
+                self._ledger_unfed()
         self.tracker.update_global_step()
         self.graph_steps += 1
         return cap.loss
