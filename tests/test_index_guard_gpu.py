@@ -16,7 +16,10 @@ Shapes: B = 3 with one duplicated cloud (cloud 1 repeats cloud 0) and one all-ze
 
 The training-only row kernels (xcorr_z0*, sa_z0*, the partial-sum finishers, pt_attn_train_bwd, unit_rows / cos_bwd_rows) are in
 tests/test_train_rows_guard_gpu.py, the fused SA / xcorr / pair kernels in tests/test_fused_guard_gpu.py, the row kernels in
-tests/test_strided_guard_gpu.py, the crop / resample / select kernels of track_ops.hip in tests/test_track_ops_guard_gpu.py,
+tests/test_strided_guard_gpu.py (ptt_rows_gemm_bnbwd_fused_f32, the one entry point on rows_gemm_kernel that file leaves out, in
+tests/test_gemm_fused_guard_gpu.py against tests/gemm_fused_ref.py; the weight packing entry points and ptt_grad_finish_f32, bit
+for bit against their restated layout and summation tree, in tests/test_pack_finish_guard_gpu.py), the crop / resample / select
+kernels of track_ops.hip in tests/test_track_ops_guard_gpu.py,
 track_losses* and the Adam pair in tests/test_step_guard_gpu.py (ptt_optim_clip_step*: tests/test_optimization_gpu.py,
 ptt_crop_scan_f32: tests/test_scan_crop_gpu.py). Out of scope of the guard-band files: ptt_box_overlap_f64 and
 ptt_train_batch_f32, which have value tests at ragged sizes of their own in tests/test_eval_metrics_gpu.py and
