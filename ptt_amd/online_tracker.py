@@ -11,11 +11,13 @@ per target from its own detector at the moment the target appears. OnlineTracker
     boxes = ot.step_raw(raw, steps=[('affine', V2C)])        # the sensor's (N, C) rows: de-interleaved and transformed on the device
 
 What a step computes for a continuing target is what TrackletRunner._steps computes for frame i of a tracklet whose clouds are
-the scans since the target's `add`, with REF_BOX = previous_result — bit for bit, because it IS the runner's code: the same
-job tables, resampling, model graph (the runner's uploaded-table branch at batch = slots) and float64 box update, driven one
-step at a time. New here are only the life cycle of the slots (SlotTable), the two resident scan buffers, and the crop
-kernel: a scan is 35k - 130k points, so the crops go through ptt_crop_scan_f32 (every job spread over the chip) from
-SCAN_CROP_MIN_POINTS points on, through ptt_crop_compact_f32 (one workgroup per job) below — identical results.
+the scans since the target's `add`, with REF_BOX = previous_result — bit for bit, because both drive the same TrackCore
+(track_core.py) at width = slots: the same job tables, resampling, model graph and float64 box update, one step at a time.
+The first-frame crops of a step's new targets are a launch of their own BEHIND the model, from a staging table of their own: the
+core's pinned table is still being read by that step's upload when they are written (so admissions=0, and TrackCore.admission_jobs
+writes into the table it is given). New here are only the life cycle of the slots (SlotTable), the two resident scan buffers,
+and the crop kernel: a scan is 35k - 130k points, so the crops go through ptt_crop_scan_f32 (every job spread over the chip)
+from SCAN_CROP_MIN_POINTS points on, through ptt_crop_compact_f32 (one workgroup per job) below — identical results.
 
     host    crop bounds of the live boxes (float64)                         -> one 2 * slots job table, one upload
     device  scan -> one of two resident (3, scan_capacity) buffers          (the previous scan stays alive: its crop around the
@@ -34,7 +36,8 @@ import torch
 
 from . import ops
 from .scene_store import check_raw
-from .tracklet_runner import TrackletRunner, tracking_modes
+from .track_core import TrackCore, unit_boxes
+from .tracklet_runner import tracking_modes
 
 # ptt_crop_scan_f32 from this many points per scan on (scan_crop=None). Measured by scripts/online_tracker_timing.py
 # (profiles/online_tracker_timing.json): the smallest measured N from which the chunked kernel is not slower at 2 jobs.
@@ -108,19 +111,15 @@ class OnlineTracker(object):
                              "OnlineTracker (first, previous and firstandprevious are supported)")
         if int(scan_capacity) < 1:
             raise ValueError("scan_capacity must be >= 1")
-        self.device = torch.device(device)
+        dev = self.device = torch.device(device)
         self.scan_capacity = int(scan_capacity)
         self.scan_crop = scan_crop
-        # the runner's buffers, tables, model graph and box update at batch = slots, on its uploaded-table branch
-        self.core = core = TrackletRunner(tracker, device, batch=slots, search_size=search_size, template_size=template_size,
-                                          search_offset=search_offset, search_scale=search_scale, model_offset=model_offset,
-                                          model_scale=model_scale, use_z=use_z, use_graph=use_graph, shape_aggregation=shape,
-                                          uploaded=True)
-        S = self.S = core.B
-        dev = self.device
+        # the step's buffers, tables, model graph and box update at width = slots; crop slots that hold a whole scan
+        self.core = core = TrackCore(tracker, device, slots, search_size, template_size, search_offset, search_scale, model_offset,
+                                     model_scale, use_z, use_graph, shape)
+        S = self.S = core.W
         self.scans = torch.zeros((2, 3, self.scan_capacity), dtype=torch.float32, device=dev)
-        core._crop_slots(self.scan_capacity)
-        self._inputs = None                                       # the model input buffers the resampling table points at
+        core.reserve(self.scan_capacity)
         # the first-frame template crops of a step's new targets: a table of their own (at most `slots` jobs)
         self.add_jobs_dev = torch.zeros(S * ops.CROP_JOB.itemsize, dtype=torch.uint8, device=dev)
         self.add_jobs_host = torch.zeros(S * ops.CROP_JOB.itemsize, dtype=torch.uint8).pin_memory()
@@ -139,15 +138,12 @@ class OnlineTracker(object):
         S = self.S
         torch.cuda.synchronize(self.device)
         self.table = SlotTable(S)
-        boxes = self.boxes = np.zeros(S, ops.TRACK_BOX)
-        boxes['wlh'], boxes['quat'][:, 0] = 1.0, 1.0              # an empty slot: a unit box, never used
+        self.boxes = unit_boxes(S)                                # an empty slot: a unit box, never used
         self.extra = np.zeros(S)                                  # wlh[1] * 0.6 of the target's initial box (the search crop's margin)
         self.rng_pos = np.zeros(S, np.int64)                      # where numpy's global generator stands for each target
         self.cur = 0                                              # the scan buffer the NEXT step fills
         self.n_prev = 0                                           # points of the previous scan
-        jobs = self.core.crop_jobs_host_np
-        jobs[:] = np.zeros((), ops.CROP_JOB)
-        jobs['capacity'] = self.core.cap
+        self.core.write_main_jobs()                               # the crop slots never move: every scan fits
 
     @property
     def targets(self):
@@ -175,30 +171,15 @@ class OnlineTracker(object):
             raise ValueError("scan of %d points, scan_capacity=%d" % (n, self.scan_capacity))
         return t, n
 
-    def _use_scan_kernel(self, n):
-        return bool(self.scan_crop) if self.scan_crop is not None else n >= SCAN_CROP_MIN_POINTS
-
-    def _crop(self, jobs_np, jobs_host, jobs_dev, n_jobs, max_points, ws):
-        """One crop launch over a host table staged in pinned memory: uploaded, then ptt_crop_scan_f32 or ptt_crop_compact_f32."""
-        chunked = self._use_scan_kernel(max_points)
-        if chunked:
-            ops.crop_scan_check(jobs_np, n_jobs, max_points)
-        jobs_dev.copy_(jobs_host, non_blocking=True)
-        if chunked:
-            ops.crop_scan_device(jobs_dev, n_jobs, max_points, ws)
-        else:
-            ops.crop_compact(jobs_dev, n_jobs)
-
-    def _model_ready(self):
-        """The model graph (captured at the first tracked step, again after the tracker's weights changed) and the resampling
-        table, which addresses the graph's static input buffers."""
-        core = self.core
-        core._drop_stale_graphs()
-        core._ensure_graph()
-        inputs = (core.search.data_ptr(), core.template.data_ptr())
-        if inputs != self._inputs:
-            ops.upload_jobs(core._resample_table(), core.reg_jobs_dev)
-            self._inputs = inputs
+    def _crop(self, max_points):
+        """-> crop(jobs, jobs_dev, n_jobs), one launch over a device table (host copy: `jobs`): ptt_crop_scan_f32 for large scans."""
+        def crop(jobs, jobs_dev, n_jobs):
+            if bool(self.scan_crop) if self.scan_crop is not None else max_points >= SCAN_CROP_MIN_POINTS:
+                ops.crop_scan_check(jobs, n_jobs, max_points)
+                ops.crop_scan_device(jobs_dev, n_jobs, max_points, self.scan_ws)
+            else:
+                ops.crop_compact(jobs_dev, n_jobs)
+        return crop
 
     # ------------------------------------------------------------------ public
     def step(self, scan, add=None, drop=()):
@@ -265,24 +246,20 @@ class OnlineTracker(object):
         boxes = self.boxes
         scores = None
         if active.any():
-            self._model_ready()
+            core.ready(self.scan_capacity)        # the model graph: captured at the first tracked step, again after the weights changed
             # the 2 * slots crop table: job 2s = this scan around target s's previous result into slot 0 (the search crop, margin
             # wlh[1] * 0.6 of its initial box), job 2s + 1 = the previous scan around it into slot 2 (get_model's previous segment)
-            jobs = core.crop_jobs_host_np
+            jobs = core.jobs
             esz, ld = 4, self.scan_capacity
             live = active.astype(bool)
             jobs['ld'] = ld
-            jobs['out'][0::2], jobs['count'][0::2] = core.out_ptr[:, 0], core.cnt_ptr[:, 0]
-            jobs['out'][1::2], jobs['count'][1::2] = core.out_ptr[:, 2], core.cnt_ptr[:, 2]
             jobs['points'][0::2] = self.scans.data_ptr() + cur * 3 * ld * esz
             jobs['points'][1::2] = self.scans.data_ptr() + prev * 3 * ld * esz
             jobs['n_points'][0::2] = np.where(live, n, 0)
             jobs['n_points'][1::2] = np.where(live, 0 if core.shape == "first" else n_prev, 0)
-            ops.track_crop_bounds(boxes, core.search_offset, core.search_scale, self.extra, jobs[0::2], job_stride=2)
-            ops.track_crop_bounds(boxes, core.model_offset, core.model_scale, None, jobs[1::2], job_stride=2)
+            core.bounds(boxes, self.extra)
             with torch.cuda.device(dev):
-                self._crop(jobs, core.crop_jobs_host, core.crop_jobs_dev, 2 * S, max(n, n_prev), self.scan_ws)
-                core._enqueue_model()
+                core.enqueue(2 * S, self._crop(max(n, n_prev)))
         if plan[1]:
             for i, s in plan[1]:
                 boxes['center'][s], boxes['wlh'][s], boxes['quat'][s] = new_boxes[i]
@@ -292,21 +269,20 @@ class OnlineTracker(object):
                 # target's life. Only their jobs: an empty job would zero the count of a continuing target's slot 1
                 k = len(plan[1])
                 slots = np.array([s for _, s in plan[1]])
-                aj = self.add_jobs_np
-                aj[:k] = np.zeros((), ops.CROP_JOB)
-                aj['points'][:k], aj['ld'][:k], aj['n_points'][:k] = self.scans.data_ptr() + cur * 3 * self.scan_capacity * 4, self.scan_capacity, n
-                aj['out'][:k], aj['count'][:k], aj['capacity'][:k] = core.out_ptr[slots, 1], core.cnt_ptr[slots, 1], core.cap
+                aj = core.admission_jobs(slots, self.add_jobs_np)
+                aj['points'], aj['ld'], aj['n_points'] = self.scans.data_ptr() + cur * 3 * self.scan_capacity * 4, self.scan_capacity, n
                 ops.track_crop_bounds(np.ascontiguousarray(boxes[slots]), core.model_offset, core.model_scale, None, aj)
                 with torch.cuda.device(dev):
-                    self._crop(aj, self.add_jobs_host, self.add_jobs_dev, k, n, self.scan_ws)
+                    self.add_jobs_dev.copy_(self.add_jobs_host, non_blocking=True)
+                    self._crop(n)(self.add_jobs_np, self.add_jobs_dev, k)
         # the pinned staging tables and the caller's scan are free again once this step's device work is done
         with torch.cuda.device(dev):
-            core._done.record(torch.cuda.current_stream(dev))
-        core._done.synchronize()
+            core.mark()
+        core.wait()
         if active.any():
-            # post_process in one call (ptt_track_select_update), as TrackletRunner._steps: box <- get_box_by_offset(box, best
-            # proposal); boxes of new and empty slots are not touched (active = 0)
-            ops.track_select_update(core.result_host.numpy(), core.info_host.numpy(), boxes, core.use_z, active, self.rng_pos, self.est_buf)
+            # post_process as TrackletRunner._steps: box <- get_box_by_offset(box, best proposal); boxes of new and empty slots are
+            # not touched (active = 0)
+            core.update(boxes, active, self.rng_pos, self.est_buf)
             scores = self.est_buf[:, 4]
         for _, s in plan[1]:
             self.rng_pos[s] = 0                   # after the update: it records the draw count of every slot's resampling, empty ones too

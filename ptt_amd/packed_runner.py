@@ -8,21 +8,21 @@ slot for its frames 1 .. L-1 and the slot goes to the next waiting tracklet in t
     results = pr.run(tracklets)             # TrackletRunner.run's input and return value, in input order
     pr.stats                                # steps, slot_steps, live_slot_steps, admissions, migrated — of that run
 
-What a step computes is what TrackletRunner._steps computes, because it IS the runner's code: its buffers, resampling table,
-model graph (the uploaded-table branch at batch = slots, what OnlineTracker drives) and float64 box update, one step at a time.
+What a step computes is what TrackletRunner._steps computes, because both drive the same TrackCore (track_core.py): its buffers,
+resampling table, model graph with the selection on the device and float64 box update, one step at a time at width = slots.
 A frame's result depends on the width the model runs at, not on the slot or the batch-mates, so with drain_slots=None every
 row is bit for bit TrackletRunner(batch=slots)'s. New here are only
 
     PackedPlan      the whole schedule, made on the host from the lengths alone (no device needed);
     admission jobs  the first-frame template crop (cloud 0 around ground-truth box 0 into crop slot 1) of the tracklets admitted
-                    in a step rides behind that step's 2 * slots crop jobs, in the same launch: frame 1 is tracked in the step
-                    of the admission. Only admitted slots get such a job (an empty one would zero a continuing slot's count);
+                    in a step rides behind that step's 2 * slots crop jobs, in the same launch (the core's table has `slots`
+                    admission entries, TrackCore.admission_jobs): frame 1 is tracked in the step of the admission;
     the drain       drain_slots=k: once nothing waits and at most k tracklets are alive they move ONCE to a second core of
                     width k (first-frame crop and its count device to device; box, generator position and frame index on the
                     host) and the run ends there: the tail costs steps of width k. A frame's bits depend on the width, so a
                     migrated tracklet's rows FROM its migration frame on are not bitwise those of the wide run.
 
-Clouds: a tracklet given as host arrays is uploaded in the step of its admission, side by side in one buffer as TrackletRunner
+Clouds: a tracklet given as host arrays goes to the device in the step of its admission, side by side in one buffer as TrackletRunner
 does (upload_clouds), and released when it finishes: at most `slots` tracklets are resident. Device tensors are used in place.
 
 Out of scope: SHAPE_AGGREGATION = all (a per-slot growing store that is reset at a refill and moved at the drain is a change of
@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .tracklet_runner import TrackletRunner, tracking_modes, upload_clouds
+from .track_core import TrackCore, unit_boxes
+from .tracklet_runner import tracking_modes, upload_clouds
 
 ORDERS = ("longest_first", "input")
 
@@ -113,41 +114,16 @@ class PackedPlan(object):
         self.admissions = len(queue)
 
 
-class _Lane(object):
-    """A TrackletRunner core of one width with what a packed step needs beside it: a crop table of 3 * width jobs (2 * width as
-    the runner's, then up to `width` admission jobs) and the per-slot boxes and generator positions."""
-
-    def __init__(self, tracker, device, width, **runner_args):
-        self.core = core = TrackletRunner(tracker, device, batch=width, uploaded=True, **runner_args)
-        W = self.W = core.B
-        nbytes = 3 * W * ops.CROP_JOB.itemsize
-        self.jobs_dev = torch.zeros(nbytes, dtype=torch.uint8, device=core.device)
-        self.jobs_host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()      # rewritten only after the step's wait
-        self.jobs_np = self.jobs_host.numpy().view(ops.CROP_JOB)
-        self.est_buf = np.zeros((W, 5), np.float32)
-        self._tables = None                                       # the buffers the uploaded resampling table points at
+class _Lane(TrackCore):
+    """A TrackCore of one width with the per-slot host state of a packed run: boxes, generator positions, chosen rows."""
 
     def start(self, cap):
-        """Before a run: crop slots that hold `cap` points, the model graph (captured at the first run, again after the tracker's
-        weights changed), the resampling table over both, the fixed fields of the crop table and fresh per-slot state."""
-        core, W = self.core, self.W
-        if getattr(core, "cap", 0) < cap:
-            core._crop_slots(cap)
-        core._drop_stale_graphs()
-        core._ensure_graph()
-        tables = (core.search.data_ptr(), core.template.data_ptr(), core.crop_out.data_ptr(), core.cap)
-        if tables != self._tables:
-            ops.upload_jobs(core._resample_table(), core.reg_jobs_dev)
-            self._tables = tables
-        jobs = self.jobs_np
-        jobs[:] = np.zeros((), ops.CROP_JOB)
-        jobs['capacity'] = core.cap
-        main = jobs[:2 * W]                                       # search crop -> slot 0, previous-frame template segment -> slot 2
-        main['out'][0::2], main['count'][0::2] = core.out_ptr[:, 0], core.cnt_ptr[:, 0]
-        main['out'][1::2], main['count'][1::2] = core.out_ptr[:, 2], core.cnt_ptr[:, 2]
-        boxes = self.boxes = np.zeros(W, ops.TRACK_BOX)
-        boxes['wlh'], boxes['quat'][:, 0] = 1.0, 1.0              # an empty slot: a unit box, never used
-        self.rng_pos = np.zeros(W, np.int64)                      # where numpy's global generator stands for each slot's tracklet
+        """Before a run: ready for clouds of `cap` points, the fixed fields of the crop table and fresh per-slot state."""
+        self.ready(cap)
+        self.write_main_jobs()
+        self.boxes = unit_boxes(self.W)                           # an empty slot: a unit box, never used
+        self.rng_pos = np.zeros(self.W, np.int64)                 # where numpy's global generator stands for each slot's tracklet
+        self.est_buf = np.zeros((self.W, 5), np.float32)
 
 
 class PackedTrackletRunner(object):
@@ -166,12 +142,10 @@ class PackedTrackletRunner(object):
         self.device = torch.device(device)
         self.slots, self.order = int(slots), order
         self.drain_slots = None if drain_slots is None else int(drain_slots)
-        args = dict(search_size=search_size, template_size=template_size, search_offset=search_offset, search_scale=search_scale,
-                    model_offset=model_offset, model_scale=model_scale, use_z=use_z, use_graph=use_graph,
-                    shape_aggregation=self.shape, ref_box=self.ref_box)
-        self.wide = _Lane(tracker, device, self.slots, **args)
-        self.drain = None if self.drain_slots is None else _Lane(tracker, device, self.drain_slots, **args)
-        self.core = self.wide.core
+        args = (search_size, template_size, search_offset, search_scale, model_offset, model_scale, use_z, use_graph, self.shape)
+        # every slot may be admitted in one step: as many admission entries as slots
+        self.core = self.wide = _Lane(tracker, device, self.slots, *args, admissions=self.slots)
+        self.drain = None if self.drain_slots is None else _Lane(tracker, device, self.drain_slots, *args, admissions=self.drain_slots)
         self.plan = None
         self.stats = dict(steps=0, slot_steps=0, live_slot_steps=0, admissions=0, migrated=0)
 
@@ -212,19 +186,18 @@ class PackedTrackletRunner(object):
         old, new = np.array([m[0] for m in moves]), np.array([m[1] for m in moves])
         dst.boxes[new], dst.rng_pos[new] = src.boxes[old], src.rng_pos[old]
         if continuing and self.shape in ("firstandprevious", "first"):
-            cap = min(src.core.cap, dst.core.cap)                 # a crop holds at most the largest cloud of the run: <= both
+            cap = min(src.cap, dst.cap)                           # a crop holds at most the largest cloud of the run: <= both
             o = torch.as_tensor([m[0] for m in continuing], device=self.device)
             n = torch.as_tensor([m[1] for m in continuing], device=self.device)
-            dst.core.crop_out[n, 1, :cap] = src.core.crop_out[o, 1, :cap]
-            dst.core.counts[n, 1] = src.core.counts[o, 1]
+            dst.crop_out[n, 1, :cap] = src.crop_out[o, 1, :cap]
+            dst.counts[n, 1] = src.counts[o, 1]
 
     # ------------------------------------------------------------------ one step
     def _step(self, lane, st):
-        core, W, dev = lane.core, lane.W, self.device
+        core, W, dev = lane, lane.W, self.device
         tr = np.array(st.track, np.int64).reshape(-1, 3)
         slots, g = tr[:, 0], self.base[tr[:, 1]] + tr[:, 2]       # the live slots and their frames' rows in the frame tables
-        jobs = lane.jobs_np
-        main = jobs[:2 * W]
+        main = core.jobs[:2 * W]
         # job 2s = cloud i of slot s's tracklet around its reference box into slot 0 (the search crop), job 2s + 1 = cloud i - 1
         # around its current result into slot 2 (get_model's previous segment); n_points = 0 for empty slots
         pts, ld, npts = np.full(2 * W, core.crop_out.data_ptr(), np.uint64), np.zeros(2 * W, np.int64), np.zeros(2 * W, np.int32)
@@ -238,35 +211,26 @@ class PackedTrackletRunner(object):
         extra[slots] = self.extra[g]
         ref = None
         if self.ref_box != "previous_result":                     # REF_BOX previous_gt / current_gt: the tracklet's own ground truth
-            ref = np.zeros(W, ops.TRACK_BOX)
-            ref['wlh'], ref['quat'][:, 0] = 1.0, 1.0
+            ref = unit_boxes(W)
             ref[slots] = self.gt[g - 1 if self.ref_box == "previous_gt" else g]
-        ops.track_crop_bounds(boxes if ref is None else ref, core.search_offset, core.search_scale, extra, main[0::2], job_stride=2)
-        ops.track_crop_bounds(boxes, core.model_offset, core.model_scale, None, main[1::2], job_stride=2)
+        core.bounds(boxes, extra, ref)
         n_jobs = 2 * W
         if st.admit and self.shape in ("firstandprevious", "first"):
             # frame 0 of the admitted tracklets: cloud 0 around ground-truth box 0 into slot 1 (get_model's first segment), fixed
             # for the tracklet's life. Their boxes still ARE box 0
-            k = len(st.admit)
             new = np.array([s for s, _ in st.admit])
             g0 = self.base[np.array([t for _, t in st.admit])]
-            aj = jobs[2 * W:2 * W + k]
+            aj = core.admission_jobs(new)
             aj['points'], aj['ld'], aj['n_points'] = self.ptr[g0], self.ld[g0], self.npts[g0]
-            aj['out'], aj['count'] = core.out_ptr[new, 1], core.cnt_ptr[new, 1]
             ops.track_crop_bounds(np.ascontiguousarray(boxes[new]), core.model_offset, core.model_scale, None, aj)
-            n_jobs += k
+            n_jobs += len(new)
         with torch.cuda.device(dev):
-            lane.jobs_dev.copy_(lane.jobs_host, non_blocking=True)
-            ops.crop_compact(lane.jobs_dev, n_jobs)
-            core._enqueue_model()
-            core._done.record(torch.cuda.current_stream(dev))
-        core._done.synchronize()
-        # post_process in one call, as TrackletRunner._steps: a REF_BOX from the ground truth is the box that moves (and keeps its wlh)
+            core.enqueue(n_jobs)
+        core.wait()
+        # post_process as TrackletRunner._steps: a REF_BOX from the ground truth is the box that moves (and keeps its wlh)
         active = np.zeros(W, np.int32)
         active[slots] = 1
-        if ref is not None:
-            boxes[slots] = ref[slots]
-        ops.track_select_update(core.result_host.numpy(), core.info_host.numpy(), boxes, core.use_z, active, lane.rng_pos, lane.est_buf)
+        core.update(boxes, active, lane.rng_pos, lane.est_buf, ref)
         res = self.rows
         res['center'][g], res['wlh'][g], res['quat'][g] = boxes['center'][slots], boxes['wlh'][slots], boxes['quat'][slots]
         self.scores[g] = lane.est_buf[slots, 4]

@@ -17,6 +17,9 @@ every tracklet per step:
             ptt_select_box_f32     best proposal of each frame                             (inside the graph)
     host    one (B,5) + (B,2,2) read-back, float64 box update of B boxes (ptt_track_box_by_offset)
 
+That step's buffers, job tables, model graph and box update are a TrackCore (track_core.py), which PackedTrackletRunner and
+OnlineTracker drive too; the runner adds the lockstep groups, the whole-frame graph of a handful of tracklets and the `all` store.
+
 At batch = 1 this is the reference's own mode (one tracklet, one frame at a time) with the per-frame PCIe traffic cut
 to ~0.5 KB; at batch = 48 it is the throughput mode for evaluating a dataset's tracklets.
 
@@ -35,7 +38,7 @@ import numpy as np
 import torch
 
 from . import graph_policy, ops
-from .hot_path import GraphedHotPath, TrackerThroughput
+from .track_core import TrackCore, unit_boxes
 
 
 SHAPE_AGGREGATIONS = ("firstandprevious", "first", "previous", "all")
@@ -77,67 +80,34 @@ def upload_clouds(clouds, dev):
     return [t if t.stride(1) == 1 else t.contiguous() for t in row]
 
 
-class _BoxedForward(object):
-    """tracker forward + best-proposal selection as ONE capturable callable: (search, template) -> (B,5) rows, the best
-    proposal of each frame picked on the device (ptt_select_box_f32) — or, select=False, all (B,P,5) proposals: at a handful of
-    tracklets the host takes the arg-max itself from the one read-back it makes anyway (np.argmax, the reference's own
-    post_process, eval_tracking_utils.py:267-269): one launch less on a chain where launches are what a frame costs."""
-
-    def __init__(self, tracker, select=True):
-        self.fwd = TrackerThroughput(tracker)
-        self.select = select
-
-    def __call__(self, search, template):
-        boxes = self.fwd(search, template)['pred_box_data'].contiguous()
-        return ops.select_box(boxes) if self.select else boxes
-
-
 class TrackletRunner(object):
     def __init__(self, tracker, device, batch=1, search_size=1024, template_size=512, search_offset=0.0,
                  search_scale=1.25, model_offset=0.0, model_scale=1.25, use_z=True, use_graph=True,
-                 shape_aggregation="firstandprevious", ref_box="previous_result", uploaded=False):
+                 shape_aggregation="firstandprevious", ref_box="previous_result"):
         """`tracker`: ptt_amd.models.trackers.PTT in eval mode on `device`. Sizes / offsets / scales are
         DATA_CONFIG.{SEARCH,TEMPLATE}_INPUT_SIZE, SEARCH_BB_*, MODEL_BB_* and USE_Z_AXIS
         (tools/cfgs/kitti_models/ptt.yaml:8-17); shape_aggregation / ref_box are TEST.SHAPE_AGGREGATION / TEST.REF_BOX
-        (:149-150), parsed by tracking_modes. uploaded=True takes the uploaded-table branch (job table in device memory,
-        model graph with the selection on the device) at a handful of tracklets too: what OnlineTracker drives."""
+        (:149-150), parsed by tracking_modes."""
         self.shape, self.ref_box = tracking_modes(shape_aggregation, ref_box)
-        self.tracker = tracker
-        self.device = torch.device(device)
-        self.B = int(batch)
-        self.S, self.T = int(search_size), int(template_size)
-        self.search_offset, self.search_scale = float(search_offset), float(search_scale)
-        self.model_offset, self.model_scale = float(model_offset), float(model_scale)
-        self.use_z = bool(use_z)
-        self.use_graph = use_graph
-        dev, B = self.device, self.B
-        self.search = torch.zeros((B, self.S, 3), dtype=torch.float32, device=dev)
-        self.template = torch.zeros((B, self.T, 3), dtype=torch.float32, device=dev)
-        self.counts = torch.zeros((B, 3), dtype=torch.int32, device=dev)          # search, first-frame, previous-frame
-        self.info = torch.zeros((B, 2, 2), dtype=torch.int32, device=dev)         # (n, draws used) of search / template
-        self.crop_jobs_dev = torch.zeros(2 * B * ops.CROP_JOB.itemsize, dtype=torch.uint8, device=dev)
-        self.crop_jobs_host = torch.zeros(2 * B * ops.CROP_JOB.itemsize, dtype=torch.uint8).pin_memory()   # staging: the
-        self.crop_jobs_host_np = self.crop_jobs_host.numpy().view(ops.CROP_JOB)   # host waits for every step's result
-        #                                                                           before it rewrites the table
-        self.reg_jobs_dev = torch.zeros(2 * B * ops.REGULARIZE_JOB.itemsize, dtype=torch.uint8, device=dev)
-        self.draws = ops.mt19937_draws(dev, max(8192, 4 * max(self.S, self.T) + 1024))
+        self.tracker, self.use_graph = tracker, use_graph
+        dev, B = self.device, self.B = torch.device(device), int(batch)
         # a handful of tracklets: the crop table rides in the crop launch's arguments (no upload), and the host picks the best
         # proposal itself from the (B,P,5) read-back — two launches less per frame of a chain that is launches
-        self.few = 2 * B <= ops.CROP_JOBS_BY_VALUE_MAX and not uploaded
-        if self.few and use_graph:
+        self.few = 2 * B <= ops.CROP_JOBS_BY_VALUE_MAX
+        self.whole = bool(self.few and use_graph)    # ... and the whole frame is ONE hipGraph (_capture_frame): the core captures none
+        info = None
+        if self.whole:
             # one read-back buffer: (B,P,5) proposals, then the (B,2,2) resampling counts
             self.P = int(tracker.box_voting_head.model_cfg.SA_CONFIG.NPOINTS)
             self.n_box = B * self.P * 5
             self.readback = torch.zeros(self.n_box + B * 4, dtype=torch.float32, device=dev)
             self.readback_host = torch.zeros(self.n_box + B * 4, dtype=torch.float32).pin_memory()
-            self.info = self.readback[self.n_box:].view(torch.int32).view(B, 2, 2)
-        self.result_host = None if self.few else torch.empty((B, 5), dtype=torch.float32).pin_memory()
-        self.info_host = torch.empty((B, 2, 2), dtype=torch.int32).pin_memory()
-        self._model = _BoxedForward(tracker, select=not self.few)
-        self._graph = None
-        self._frame = None                                           # few tracklets: crops + resampling + model + read-backs, one graph
-        self._watch = None                                           # the tracker's state as of the graph's capture (ops.StateWatch)
-        self._done = torch.cuda.Event()
+            info = self.readback[self.n_box:].view(torch.int32).view(B, 2, 2)
+        self.core = TrackCore(tracker, dev, B, search_size, template_size, search_offset, search_scale, model_offset, model_scale,
+                              use_z, use_graph and not self.few, self.shape, few=self.few, info=info)
+        self.S, self.T, self._model = self.core.S, self.core.T, self.core.model
+        # few tracklets: crops + resampling + model + read-backs as one graph, and the tracker's state as of its capture (ops.StateWatch)
+        self._frame = self._watch = None
         # SHAPE_AGGREGATION = all: per tracklet the canonical-frame crops of frames 0..i-1, (B, capacity, 3), and their running
         # totals (device scalars the append crop raises; the host learns them from the template's read-back info[0])
         self.store = self.store_count = None
@@ -145,32 +115,29 @@ class TrackletRunner(object):
         self.stream = None                                           # run_overlapped gives every runner its own stream
         self.profile = None       # set to {} before run(): per-frame host_pre / device / host_post milliseconds are appended
 
+    draws = property(lambda self: self.core.draws, lambda self, table: setattr(self.core, "draws", table))     # the core's draw table
+
     # ------------------------------------------------------------------ device buffers of one group of tracklets
     def _load(self, tracklets):
         """tracklets: list (<= batch) of (clouds, boxes): clouds = list of (3,N_i) float32 arrays / tensors, boxes =
         list of (center (3), wlh (3), quat (4)) ground-truth boxes (frame 0 initialises; wlh[1] enters the search crop,
         eval_tracking_utils.py:165-169)."""
-        dev, B = self.device, self.B
-        self._ensure_graph()
+        dev, B, core = self.device, self.B, self.core
         T = max(len(c) for c, _ in tracklets)
         self.clouds = []
-        self.ptr = np.zeros((T, B), np.uint64)
-        self.ld = np.zeros((T, B), np.int64)
-        self.npts = np.zeros((T, B), np.int32)
+        # per frame i the cloud fields (address, row stride, points) of the interleaved 2B-job table: even jobs = frame i ...
+        ff = [np.zeros((T, 2 * B), dt) for dt in (np.uint64, np.int64, np.int32)]
         cap = 1
         for b, (clouds, _) in enumerate(tracklets):
             row = upload_clouds(clouds, dev)
             for i, t in enumerate(row):
-                self.ptr[i, b], self.ld[i, b], self.npts[i, b] = t.data_ptr(), t.stride(0), t.shape[1]
+                ff[0][i, 2 * b], ff[1][i, 2 * b], ff[2][i, 2 * b] = t.data_ptr(), t.stride(0), t.shape[1]
                 cap = max(cap, t.shape[1])
             self.clouds.append(row)
-        self._crop_slots(cap)
-        self.ptr[self.npts == 0] = self.crop_out.data_ptr()        # empty jobs still carry a valid address
-        # per tracked frame i the cloud fields of the interleaved 2B-job table: even jobs = frame i, odd jobs = frame i - 1
-        ff = [np.zeros((T, 2 * B), dt) for dt in (np.uint64, np.int64, np.int32)]
-        for dst, src in zip(ff, (self.ptr, self.ld, self.npts)):
-            dst[:, 0::2] = src
-            dst[1:, 1::2] = src[:-1]
+        core.ready(cap)
+        ff[0][ff[2] == 0] = core.crop_out.data_ptr()               # empty jobs still carry a valid address
+        for f in ff:
+            f[1:, 1::2] = f[:-1, 0::2]                             # ... odd jobs = frame i - 1
         if self.shape == "first":
             ff[2][:, 1::2] = 0                                     # the template is frame 0's crop alone: no per-frame crop
         elif self.shape == "all":
@@ -178,7 +145,6 @@ class TrackletRunner(object):
             lengths = np.array([len(c) for c, _ in tracklets] + [0] * (B - len(tracklets)))
             ff[2][:, 1::2] *= (np.arange(T)[:, None] < lengths[None, :])
         self.frame_fields = ff
-        rj = self._resample_table()
         if self.shape == "all":
             # every group starts with an empty store; a store that grew in an earlier group keeps its capacity
             if self.store is None or self.store.shape[1] < cap:
@@ -186,40 +152,7 @@ class TrackletRunner(object):
                 self.store_count = torch.zeros(B, dtype=torch.int32, device=dev)
             self.store_count.zero_()
             self.store_total = np.zeros(B, np.int64)
-            self._store_tables()                                   # uploads the resampling table
-        else:
-            ops.upload_jobs(rj, self.reg_jobs_dev)
-
-    def _crop_slots(self, cap):
-        """The crop outputs of every tracklet, (B, 3, cap, 3): slot 0 search, 1 first-frame, 2 previous-frame template segment,
-        with the job tables' pointers to the slots (out_ptr) and to their device counts (cnt_ptr), both (B, 3)."""
-        B = self.B
-        self.cap = cap
-        self.crop_out = torch.zeros((B, 3, cap, 3), dtype=torch.float32, device=self.device)
-        esz = self.crop_out.element_size()
-        self.out_ptr = (self.crop_out.data_ptr() + (np.arange(B)[:, None] * 3 + np.arange(3)[None]) * (cap * 3 * esz)).astype(np.uint64)
-        self.cnt_ptr = (self.counts.data_ptr() + (np.arange(B)[:, None] * 3 + np.arange(3)[None]) * 4).astype(np.uint64)
-
-    def _resample_table(self):
-        """The 2B resampling jobs (job 2b: tracklet b's search cloud, 2b + 1: its template) over the current crop slots and model
-        input buffers -> self.reg_jobs. They never change within a group: fixed segment / output pointers."""
-        B, cap = self.B, self.cap
-        rj = np.zeros(2 * B, ops.REGULARIZE_JOB)
-        s, t = rj[0::2], rj[1::2]
-        s['seg'][:, 0], s['seg_count'][:, 0], s['seg_capacity'][:, 0] = self.out_ptr[:, 0], self.cnt_ptr[:, 0], cap
-        s['n_seg'], s['input_size'] = 1, self.S
-        s['out'] = self.search.data_ptr() + np.arange(B) * (self.S * 3 * 4)
-        s['info'] = self.info.data_ptr() + np.arange(B) * 16
-        # the template's segments in get_model's order (prepare_template :187-216): firstandprevious [PC_0, PC_{i-1}], first [PC_0],
-        # previous [PC_{i-1}] — slot 1 holds frame 0's crop, slot 2 the per-frame crop; all: the tracklet's store (_store_tables)
-        slots = {"firstandprevious": (1, 2), "first": (1,), "previous": (2,), "all": ()}[self.shape]
-        for k, slot in enumerate(slots):
-            t['seg'][:, k], t['seg_count'][:, k], t['seg_capacity'][:, k] = self.out_ptr[:, slot], self.cnt_ptr[:, slot], cap
-        t['n_seg'], t['input_size'] = max(1, len(slots)), self.T
-        t['out'] = self.template.data_ptr() + np.arange(B) * (self.T * 3 * 4)
-        t['info'] = self.info.data_ptr() + np.arange(B) * 16 + 8
-        self.reg_jobs = rj
-        return rj
+            self._store_tables()
 
     def _store_tables(self):
         """SHAPE_AGGREGATION = all: point the template crop jobs (odd entries of the pinned crop table: append into the store) and
@@ -229,10 +162,10 @@ class TrackletRunner(object):
         B, cap = self.B, self.store.shape[1]
         ptr = (self.store.data_ptr() + np.arange(B) * (cap * 3 * 4)).astype(np.uint64)
         cnt = (self.store_count.data_ptr() + np.arange(B) * 4).astype(np.uint64)
-        t = self.reg_jobs[1::2]
+        t = self.core.reg_jobs[1::2]
         t['seg'][:, 0], t['seg_count'][:, 0], t['seg_capacity'][:, 0] = ptr, cnt, cap
         self.store_jobs = (ptr, cnt, cap)
-        ops.upload_jobs(self.reg_jobs, self.reg_jobs_dev)
+        self.core.upload_resampling()
 
     def _reserve_store(self, i):
         """Before frame i appends cloud i - 1: every store must hold its total plus all of that cloud's points (a crop keeps
@@ -248,102 +181,75 @@ class TrackletRunner(object):
         self.store = grown
         self.store_growths += 1
         self._store_tables()
-        jobs = self.crop_jobs_host_np[1::2]
+        jobs = self.core.jobs[1::2]
         jobs['out'], jobs['capacity'] = self.store_jobs[0], self.store_jobs[2]
 
-    def _crop_jobs(self, frame_a, slot_a, cfg_a, frame_b, slot_b, cfg_b, launch=True):
-        """The 2B-entry crop table of one step, built in the pinned staging buffer and copied to the device: job 2b =
-        cloud `frame_a` of tracklet b cropped around the tracklet's current box into slot_a, job 2b+1 likewise (frame
-        None / past the tracklet's end: an empty job -> count 0 -> an all-zero resampled cloud). cfg = (offset, scale,
-        extra2 | None); the float64 bounds come from ptt_track_crop_bounds (microseconds for 48 boxes)."""
-        jobs = self.crop_jobs_host_np
-        for k, (frame, slot, cfg) in enumerate(((frame_a, slot_a, cfg_a), (frame_b, slot_b, cfg_b))):
-            half = jobs[k::2]
-            half['out'], half['count'], half['append'] = self.out_ptr[:, slot], self.cnt_ptr[:, slot], 0
-            if frame is None or frame >= self.ptr.shape[0]:
-                half['points'], half['n_points'] = self.crop_out.data_ptr(), 0
-                continue
-            half['points'], half['ld'], half['n_points'] = self.ptr[frame], self.ld[frame], self.npts[frame]
-            ops.track_crop_bounds(self.boxes, cfg[0], cfg[1], cfg[2], half, job_stride=2)
-        if self.few and self.use_graph and launch is False:
-            return                                   # the frame graph reads the pinned table itself
-        if self.few:
-            ops.crop_compact_host(jobs, 2 * self.B, self.device)
-        else:
-            self.crop_jobs_dev.copy_(self.crop_jobs_host, non_blocking=True)
-            ops.crop_compact(self.crop_jobs_dev, 2 * self.B)
+    def _first_frame_crop(self):
+        """Frame 0: cloud 0 of every tracklet cropped around its ground-truth box 0 into slot 1 (get_model's first segment, fixed
+        for the whole tracklet) — the even entries of the crop table; the odd ones are empty jobs (count 0) into slot 2."""
+        core = self.core
+        core.write_main_jobs()
+        first = core.admission_jobs(np.arange(self.B), core.jobs[0::2])
+        first['points'], first['ld'], first['n_points'] = (f[0, 0::2] for f in self.frame_fields)
+        ops.track_crop_bounds(self.boxes, core.model_offset, core.model_scale, None, first, job_stride=2)
+        core.jobs['points'][1::2] = core.crop_out.data_ptr()
+        core.crop(2 * self.B)
 
     def _frame_jobs(self, i, extra2, ref=None):
-        """The crop table of tracked frame i >= 1 written into the pinned staging buffer with three array assignments and two
-        calls: job 2b = cloud i of tracklet b around its reference box into slot 0 (the search crop, `extra2` = gt_wlh1 * 0.6;
+        """The crop table of tracked frame i >= 1 written into the pinned staging buffer with three array assignments and the
+        core's two bounds calls: job 2b = cloud i of tracklet b around its reference box into slot 0 (the search crop, `extra2` = gt_wlh1 * 0.6;
         `ref` = the REF_BOX boxes, None = the current results), job 2b + 1 = cloud i - 1 around its current result into slot 2
         (get_model's previous-frame segment) or appended to its store (all). The per-frame cloud fields were laid out for
         all frames by _load (self.frame_fields); `out` / `count` were set for these slots once (_steps)."""
-        jobs = self.crop_jobs_host_np
+        jobs = self.core.jobs
         pts, ld, npts = self.frame_fields
         jobs['points'], jobs['ld'], jobs['n_points'] = pts[i], ld[i], npts[i]
-        ops.track_crop_bounds(self.boxes if ref is None else ref, self.search_offset, self.search_scale, extra2, jobs[0::2],
-                              job_stride=2)
-        ops.track_crop_bounds(self.boxes, self.model_offset, self.model_scale, None, jobs[1::2], job_stride=2)
-
-    def _launch_jobs(self):
-        jobs = self.crop_jobs_host_np
-        if self.few:
-            ops.crop_compact_host(jobs, 2 * self.B, self.device)
-        else:
-            self.crop_jobs_dev.copy_(self.crop_jobs_host, non_blocking=True)
-            ops.crop_compact(self.crop_jobs_dev, 2 * self.B)
+        self.core.bounds(self.boxes, extra2, ref)
 
     # ------------------------------------------------------------------ one group in lockstep
     def _steps(self, tracklets):
         """Generator form of one lockstep group: every `yield` sits between "frame i's device work is enqueued" and
         "the host waits for it", so that a driver can enqueue ANOTHER group's frame in between (run_overlapped). The
         generator's return value (StopIteration.value) is the group's result list."""
-        B = self.B
-        n = len(tracklets)
+        B, core, n = self.B, self.core, len(tracklets)
         self._load(tracklets)
         lengths = np.array([len(c) for c, _ in tracklets] + [0] * (B - n))
         T = int(lengths.max())
-        boxes = self.boxes = np.zeros(B, ops.TRACK_BOX)
-        boxes['wlh'], boxes['quat'][:, 0] = 1.0, 1.0
+        boxes = self.boxes = unit_boxes(B)
         gt_wlh1 = np.zeros((T, B))
-        gt = None
-        if self.ref_box != "previous_result":
-            gt = np.zeros((T, B), ops.TRACK_BOX)                 # REF_BOX previous_gt / current_gt: frame i's reference box
-            gt['wlh'], gt['quat'][..., 0] = 1.0, 1.0              # (frames past a tracklet's end: a unit box, never used)
+        # REF_BOX previous_gt / current_gt: frame i's reference box (frames past a tracklet's end: a unit box, never used)
+        gt = None if self.ref_box == "previous_result" else unit_boxes((T, B))
         for b, (_, gts) in enumerate(tracklets):
             boxes['center'][b], boxes['wlh'][b], boxes['quat'][b] = gts[0][0], gts[0][1], gts[0][2]
             for i, bx in enumerate(gts):
                 gt_wlh1[i, b] = bx[1][1]
                 if gt is not None:
                     gt['center'][i, b], gt['wlh'][i, b], gt['quat'][i, b] = bx[0], bx[1], bx[2]
-        self.crop_jobs_host_np['capacity'] = self.cap
         # per step: whole-batch copies (a result taken from a ground-truth reference box carries that box's wlh)
         history = [(np.ones(B, np.int32), boxes['center'].copy(), boxes['wlh'].copy(), boxes['quat'].copy(), None)]
         rng_pos = np.zeros(B, np.int64)            # where numpy's global generator stands for each tracklet
-        model_cfg = (self.model_offset, self.model_scale, None)
-
-        # frame 0: the first-frame template crop (get_model's first segment, slot 1) is fixed for the whole tracklet. Only
-        # firstandprevious and first read slot 1: previous resamples slot 2 alone, and all takes frame 0's crop from its store,
-        # to which frame 1 appends it — no launch for those two
+        # frame 0: the first-frame template crop is fixed for the whole tracklet. Only firstandprevious and first read slot 1:
+        # previous resamples slot 2 alone, and all takes frame 0's crop from its store, to which frame 1 appends it — no launch
+        # for those two
         if self.shape in ("firstandprevious", "first"):
-            self._crop_jobs(0, 1, model_cfg, None, 2, model_cfg)
+            self._first_frame_crop()
         # the job table travels through ONE pinned staging buffer: its copy must have left the host before frame 1's
         # table is written into it (every later frame waits for its boxes anyway)
-        self._done.record(torch.cuda.current_stream(self.device))
-        self._done.synchronize()
-        # every tracked frame crops into the same slots: search -> 0, previous-frame template segment -> 2
-        jobs = self.crop_jobs_host_np
-        jobs['out'][0::2], jobs['count'][0::2] = self.out_ptr[:, 0], self.cnt_ptr[:, 0]
-        jobs['out'][1::2], jobs['count'][1::2] = self.out_ptr[:, 2], self.cnt_ptr[:, 2]
-        jobs['append'] = 0
+        core.mark()
+        core.wait()
+        core.write_main_jobs()                                    # every tracked frame crops into the same slots
         if self.shape == "all":                                  # ... or the template crop appends to the tracklet's store
+            jobs = core.jobs
             jobs['out'][1::2], jobs['count'][1::2], jobs['capacity'][1::2] = self.store_jobs
             jobs['append'][1::2] = 1
         extra_search = np.ascontiguousarray(gt_wlh1 * 0.6)        # (T, B): gt_box.wlh[1] * 0.6 enters the search crop (:321)
         est_buf = np.zeros((B, 5), np.float32)
         active_all = (np.arange(T)[:, None] < lengths[None, :]).astype(np.int32)
-        views = None                                             # numpy views of the pinned read-back buffers, made once
+        whole, read, info = self.whole, None, core.info_host.numpy()
+        if whole:                                                # one read-back buffer: (B,P,5) proposals, then the resampling counts
+            host = self.readback_host.numpy()
+            info = host[self.n_box:].view(np.int32).reshape(B, 2, 2)
+            read = (host[:self.n_box].reshape(B, self.P, 5), info)
 
         prof = self.profile
         if prof is not None:
@@ -362,41 +268,24 @@ class TrackletRunner(object):
             ref = None if gt is None else gt[i - 1] if self.ref_box == "previous_gt" else gt[i]
             if self.shape == "all":
                 self._reserve_store(i)
-            if self.few and self.use_graph:
+            self._frame_jobs(i, extra_search[i], ref)
+            if whole:
                 # a handful of tracklets: the WHOLE frame is one hipGraph replay — crops (their table read from pinned host
                 # memory, rewritten here), resampling, read-back of the draw counts, tracker, read-back of the proposals
-                self._frame_jobs(i, extra_search[i], ref)
                 if self._frame is None:
                     self._capture_frame()
                 self._frame.replay()
+                core.mark()
             else:
-                self._frame_jobs(i, extra_search[i], ref)
-                self._launch_jobs()
-                self._enqueue_model()
-            self._done.record(torch.cuda.current_stream(self.device))
+                core.enqueue(2 * B)
             if prof is not None:
                 ev1.record(torch.cuda.current_stream(self.device))
                 t_b = time.perf_counter()
             yield i
-            self._done.synchronize()
+            core.wait()
             if prof is not None:
                 t_c = time.perf_counter()
-            if self.few and self.use_graph:                      # one buffer: (B,P,5) proposals, then the resampling counts
-                if views is None:
-                    host = self.readback_host.numpy()
-                    views = (host[:self.n_box].reshape(B, self.P, 5), host[self.n_box:].view(np.int32).reshape(B, 2, 2))
-            elif views is None or views[2] is not self.result_host:
-                # (B,5) float32: x, y, z, theta (degrees), score
-                views = (self.result_host.numpy(), self.info_host.numpy(), self.result_host)
-            est, info = views[0], views[1]
-            # post_process (:266-274) in one call (ptt_track_select_update): the first arg-max of the scores where the read-back is
-            # (B,P,5) (:267-269), box_i = get_box_by_offset(box_{i-1}, best proposal, USE_Z_AXIS). An implausibly large x / y offset
-            # is redrawn from numpy's GLOBAL generator (:205-208), whose state then is "seeded with 1 and advanced by the template's
-            # (else the search's) resampling draws" — the draw counts come back with the boxes; a draw table that ran out raises
-            if ref is not None:                                  # post_process :270 moves the REF box (and keeps its wlh)
-                live = active.astype(bool)
-                boxes[live] = ref[live]
-            ops.track_select_update(est, info, boxes, self.use_z, active, rng_pos, est_buf)
+            core.update(boxes, active, rng_pos, est_buf, ref, read)   # post_process (:266-274)
             if self.shape == "all":                              # the template's n is the store's new total (one segment)
                 self.store_total[:] = info[:, 1, 0]
             history.append((active, boxes['center'].copy(), boxes['wlh'].copy(), boxes['quat'].copy(), est_buf[:, 4].copy()))
@@ -425,18 +314,10 @@ class TrackletRunner(object):
             except StopIteration as stop:
                 return stop.value
 
-    def _enqueue_model(self):
-        """Behind a frame's crop launch: resampling into the model's input buffers, the model, and the two read-backs."""
-        ops.regularize(self.reg_jobs_dev, 2 * self.B, self.draws)
-        self.info_host.copy_(self.info, non_blocking=True)       # behind the resampling, ahead of the model: off the frame's tail
-        rows = self._forward()
-        if self.result_host is None or self.result_host.shape != rows.shape:
-            self.result_host = torch.empty(tuple(rows.shape), dtype=torch.float32).pin_memory()
-        self.result_host.copy_(rows, non_blocking=True)
-
     def _frame_body(self):
-        ops.crop_regularize_pinned(self.crop_jobs_host, self.reg_jobs_dev, 2 * self.B, self.draws)     # crop w, then resampling w
-        rows = self._model(self.search, self.template)
+        core = self.core
+        ops.crop_regularize_pinned(core.jobs_host, core.reg_jobs_dev, 2 * self.B, core.draws)     # crop w, then resampling w
+        rows = self._model(core.search, core.template)
         if rows.data_ptr() != self.readback.data_ptr():      # a box head that did not take the preallocated output: one copy
             self.readback[:self.n_box].view(self.B, self.P, 5).copy_(rows)
         return rows
@@ -444,8 +325,8 @@ class TrackletRunner(object):
     def _capture_frame(self):
         """One frame of a handful of tracklets as ONE hipGraph: called at the first tracked frame of the first group, when the
         job tables hold valid pointers (the warm-up runs execute them). The box head writes its proposals straight into the
-        read-back buffer whose tail the resampling kernel fills with its draw counts (`self.info` lives there): ONE device-to-
-        host copy per frame."""
+        read-back buffer whose tail the resampling kernel fills with its draw counts (the core's `info` lives there): ONE
+        device-to-host copy per frame."""
         head = self.tracker.box_voting_head
         with torch.no_grad():
             cur = torch.cuda.current_stream(self.device)
@@ -459,7 +340,7 @@ class TrackletRunner(object):
             try:
                 with torch.cuda.stream(side):
                     for _ in range(3):                       # weight packing / LDS attributes happen here, not in capture
-                        rows = self._frame_body()
+                        self._frame_body()
                 cur.wait_stream(side)
                 torch.cuda.synchronize(self.device)
                 if totals is not None:
@@ -472,29 +353,12 @@ class TrackletRunner(object):
             finally:
                 head.pred_box_out = None                     # the tracker may be shared: the hook is only live during capture
 
-    def _ensure_graph(self):
-        """The tracker forward + box selection for B frames as a hipGraph whose static inputs ARE the buffers the
-        resampling kernel writes (no staging copy)."""
-        if self.few:
-            return                                           # the frame graph (_capture_frame) holds the model
-        if self.use_graph and self._graph is None:
-            with torch.no_grad():
-                self._graph = GraphedHotPath(self._model, self.search, self.template, watch=False)     # run() checks the tracker
-            self.search, self.template = self._graph.search, self._graph.template
-            self._watch = ops.StateWatch(self.tracker)
-
     def _drop_stale_graphs(self):
-        """Once per run (the weights cannot change inside one): a graph captured before the tracker's weights or cached parameters
-        changed (load_state_dict, training, train() / eval()) would replay the old weights, or read freed buffers — it is dropped
-        and captured again at the next frame."""
+        """Once per run (the weights cannot change inside one): a frame graph captured before the tracker's weights or cached parameters
+        changed would replay the old weights, or read freed buffers — it is dropped and captured again at the next frame (the core
+        checks its model graph itself, TrackCore.ready)."""
         if self._watch is not None and self._watch.changed():
-            self._frame = self._graph = self._watch = None
-
-    def _forward(self):
-        with torch.no_grad():
-            if not self.use_graph:
-                return self._model(self.search, self.template)
-            return self._graph()                                  # inputs are already in the graph's static buffers
+            self._frame = self._watch = None
 
     # ------------------------------------------------------------------ public
     def run(self, tracklets):
@@ -525,36 +389,26 @@ def run_overlapped(runners, tracklets):
             r.stream = torch.cuda.Stream(device=dev)
         r._drop_stale_graphs()
     # deal whole groups round-robin: runner k takes groups k, k+R, ...
-    order, per_runner = [], [[] for _ in runners]
-    pos = 0
-    k = 0
+    queues = [[] for _ in runners]
+    pos = k = 0
     while pos < len(tracklets):
         b = runners[k % R].B
-        per_runner[k % R].append((pos, tracklets[pos:pos + b]))
+        queues[k % R].append((pos, tracklets[pos:pos + b]))
         pos += b
         k += 1
     results = [None] * len(tracklets)
-    queues = [list(g) for g in per_runner]
     active = [None] * R                                             # (generator, start index) of the group in flight
     while any(queues) or any(a is not None for a in active):
         for r, runner in enumerate(runners):
             if active[r] is None and queues[r]:
                 start, group = queues[r].pop(0)
-                with torch.cuda.stream(runner.stream):
-                    gen = runner._steps(group)
-                    try:
-                        next(gen)                                   # enqueue the first frame
-                        active[r] = (gen, start)
-                    except StopIteration as stop:                   # single-frame tracklets: nothing to track
-                        for j, res in enumerate(stop.value):
-                            results[start + j] = res
-            elif active[r] is not None:
+                active[r] = (runner._steps(group), start)           # a generator: nothing of it has run yet
+            if active[r] is not None:
                 gen, start = active[r]
                 with torch.cuda.stream(runner.stream):
                     try:
-                        next(gen)                                   # wait for this group's frame, enqueue its next one
-                    except StopIteration as stop:
-                        for j, res in enumerate(stop.value):
-                            results[start + j] = res
+                        next(gen)                                   # wait for this group's frame (if any), enqueue its next one
+                    except StopIteration as stop:                   # at once for single-frame tracklets: nothing to track
+                        results[start:start + len(stop.value)] = stop.value
                         active[r] = None
     return results

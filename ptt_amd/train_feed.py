@@ -41,6 +41,7 @@ import torch
 from . import ops
 from .datasets.augmentor import DataAugmentor, augmentor_utils
 from .datasets.kitti import box_math as bm
+from .track_core import slot_pointers
 from .tracklet_shard import dist_info, shard_indices
 
 _MVN = None
@@ -414,8 +415,7 @@ class TrainBatchFeeder(TrainBatchPlan):
         self.table_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.cands_dev = self.table_dev[self.jobs_bytes:]
         self.aug_dev = self.table_dev[aug_at:] if self.aug_steps is not None else None
-        out_ptr = (self.crop_out.data_ptr() + (np.arange(C)[:, None] * 3 + np.arange(3)[None]) * (cap * 12)).astype(np.uint64)
-        cnt_ptr = (self.counts.data_ptr() + (np.arange(C)[:, None] * 3 + np.arange(3)[None]) * 4).astype(np.uint64)
+        out_ptr, cnt_ptr = slot_pointers(self.crop_out.data_ptr(), self.counts.data_ptr(), C, cap)
         lab_ptr = (self.labels.data_ptr() + np.arange(C) * cap).astype(np.uint64)
         self._staging = []
         for _ in range(self.depth):

@@ -217,10 +217,10 @@ def test_load_state_dict_between_steps_recaptures(dev):
     ot = OnlineTracker(tracker, dev, slots=2, scan_capacity=CAPACITY, shape_aggregation="previous")
     ot.step(scans[0], add={"A": boxes[0][0]})
     after1 = ot.step(scans[1])["A"]
-    graph = ot.core._graph
+    graph = ot.core.graph
     tracker.load_state_dict(new.state_dict())
     got = ot.step(scans[2])["A"]
-    assert ot.core._graph is not graph and ot.core._graph.captures == 1          # a new capture, not a replay of the old weights
+    assert ot.core.graph is not graph and ot.core.graph.captures == 1          # a new capture, not a replay of the old weights
     fresh = OnlineTracker(new, dev, slots=2, scan_capacity=CAPACITY, shape_aggregation="previous")
     fresh.step(scans[1], add={"A": after1[:3]})
     _same(got, fresh.step(scans[2])["A"], "step 2 with the new weights")

@@ -126,11 +126,11 @@ def test_a_second_run_and_new_weights(dev):
     want = _expected(dev, 2)
     _all_same(pr.run(_tracklets()), want, "first run")
     _all_same(pr.run(_tracklets()[::-1])[::-1], want, "second run, tracklets reversed")
-    graph = pr.core._graph
+    graph = pr.core.graph
     new = _make_tracker(dev, seed=3)
     tracker.load_state_dict(new.state_dict())
     got = pr.run(_tracklets())
-    assert pr.core._graph is not graph and pr.core._graph.captures == 1
+    assert pr.core.graph is not graph and pr.core.graph.captures == 1
     _all_same(got, _oracle_rows(new, dev, 2), "new weights")
     assert not np.array_equal(got[3][-1][0], want[3][-1][0])                         # ... and not what the old weights give
 
