@@ -326,7 +326,8 @@ typedef struct ptt_sa_desc {
     int64_t out_sb, out_sc, out_sm;    /* element strides of out[b][c][m]              */
     int B, N, M, nsample, C;           /* nsample 16, 32 or 64 (PTT_EUNSUPPORTED otherwise) */
     float radius;
-    int use_xyz;          /* prepend the 3 relative coordinates (reference default)    */
+    int use_xyz;          /* prepend the 3 relative coordinates (reference default); with C == 0 it must be 1:
+                           * a level needs the coordinates or point features (PTT_EINVAL otherwise) */
     int normalize_xyz;    /* divide them by radius (pointnet2_utils.py:353-354)        */
     int n_layers;
     ptt_sa_layer layers[PTT_SA_MAX_LAYERS];
@@ -335,7 +336,7 @@ typedef struct ptt_sa_desc {
      *   T  = scale0 * (W0[:,3:] . f_n) + shift0     one row per POINT (ptt_linear_f32), (B,N,C0) contiguous
      *   Wx = (scale0 * W0[:, 0:3])^T                (3,C0)
      * which moves 2*C*C0 flop per grouped row (N*... rows instead of M*nsample) out of the kernel.
-     * When l0_point_term != NULL: use_xyz must be 1, feat/C are ignored and `layers` holds the REMAINING layers
+     * When l0_point_term != NULL: use_xyz must be 1 (PTT_EINVAL otherwise), feat/C are ignored and `layers` holds the REMAINING layers
      * (layers[0].Cin == l0_channels). NULL = layer 0 runs inside the kernel on the gathered rows. */
     const float* l0_point_term;
     const float* l0_xyz_weight;

@@ -16,6 +16,10 @@ dominated by the rounding of the final store (the one-centre case measures 7e-8,
 checks the pair (0 < e32 <= 2e-6) and the ragged property every case is listed for; tests/test_fused_guard_gpu.py holds the
 kernels to R * Y.
 
+The set-abstraction reference takes every option of ptt_sa_desc (sa_ref: use_xyz, normalize_xyz, per-layer ReLU, l0_relu,
+layers without BatchNorm) in float64 and in float32, and SA_OPTION_CASES puts the shapes of SA_CASES on clouds whose balls hold
+distinct points (cube_clouds) with one option set each: tests/test_sa_options_gpu.py, tests/test_sa_module_options_gpu.py.
+
 Cases are built once per process (functools.lru_cache) and shared; nothing mutates them."""
 import functools
 import math
@@ -81,12 +85,15 @@ SA_CASES = {
 }
 
 
-def sa_dispatch(B, M, C, spec, ns, scale_in_weights, hoisted):
+def sa_dispatch(B, M, C, spec, ns, scale_in_weights, hoisted, use_xyz=True, relu0=True, relu1=True):
     """The kernel ptt_sa_fused_fwd_f32 launches for a level, restated from its dispatch (mfma_ops.hip: the chain of `if`s
-    after `const int total_centres = d->B * d->M;`) -> (name, facts about the launch's tiles)."""
+    after `const int total_centres = d->B * d->M;`) -> (name, facts about the launch's tiles). spec is the channel list of
+    the whole SharedMLP (spec[0] = 3 * use_xyz + C); scale_in_weights: no layer the kernel runs carries a scale pointer;
+    relu0 / relu1: `L[0].relu` / `L[1].relu` of the layers the KERNEL runs (with a hoisted layer 0 those are layers 1 and 2 of
+    the SharedMLP) — the only activation flags the dispatch reads."""
     total = B * M
     louts = spec[1:]
-    if C == 0 and not hoisted and ns == 32 and louts == [64, 64, 128] and scale_in_weights:
+    if C == 0 and use_xyz and not hoisted and ns == 32 and louts == [64, 64, 128] and scale_in_weights and relu0 and relu1:
         chunk = min(-(-total // SAL_DEVICE_WAVES), SAL_CHUNK_MAX)
         nw = 4 if total * 3 <= SAL_DEVICE_WAVES else SAL_WAVES
         wgs = -(-total // (chunk * nw))
@@ -99,7 +106,7 @@ def sa_dispatch(B, M, C, spec, ns, scale_in_weights, hoisted):
         per_wg = 4 * cpw
         wgs = -(-total // per_wg)
         return "sa_wave_kernel<%d,1>" % ns, dict(total=total, cpw=cpw, per_wg=per_wg, wgs=wgs, last_wg=total - (wgs - 1) * per_wg)
-    if hoisted and spec[1] == 128 and ns == 32 and rem == [128, 256] and scale_in_weights:
+    if hoisted and spec[1] == 128 and ns == 32 and rem == [128, 256] and scale_in_weights and relu0:
         tiles = (total + 1) // 2
         wgs = min(tiles, STREAM_MAX_WGS)
         chunk = min(-(-tiles // wgs), STREAM_CHUNK_MAX)
@@ -122,14 +129,47 @@ def _sa_gather64(t, idx):
     return torch.gather(t, 2, flat).reshape(B, t.shape[1], M, ns)
 
 
-def sa_ref64(xyz, new_xyz, feats, idx, layers, radius, ns):
-    """oracle.dense_ref.query_and_group (use_xyz, normalize_xyz) + shared_mlp_eval + max-pool in float64 on a fixed idx."""
-    x, c = xyz.double(), new_xyz.double()
+def mlp_eval(x, layers, relu=None):
+    """oracle.dense_ref.shared_mlp_eval (pytorch_utils.py:12-36) with the options of pt_utils.Conv2d spelled out: a layer
+    dict without bn_* keys is a unit built with bn=False (its conv_bias, when present, is the convolution's bias), and
+    relu[l] False a unit built with activation=None. relu=None on BatchNorm layers is shared_mlp_eval itself, op for op."""
+    for l, L in enumerate(layers):
+        x = F.conv2d(x, L["conv_weight"], L.get("conv_bias"))
+        if "bn_weight" in L:
+            x = F.batch_norm(x, L["bn_mean"], L["bn_var"], L["bn_weight"], L["bn_bias"], False, 0.0, L.get("eps", 1e-5))
+        if relu is None or relu[l]:
+            x = F.relu(x)
+    return x
+
+
+def sa_ref(xyz, new_xyz, feats, idx, layers, radius, ns, use_xyz=True, normalize_xyz=True, relu=None, l0_relu=None,
+           dtype=torch.float64):
+    """QueryAndGroup (pointnet2_utils.py:350-368: use_xyz, normalize_xyz) + SharedMLP in eval mode + max-pool on a fixed idx,
+    in `dtype`: float64 is the reference, float32 its twin — the same ops on the same table, which is
+    oracle.dense_ref.query_and_group + shared_mlp_eval bit for bit (tests/test_fused_ref_cpu.py). relu: one flag per layer
+    (None = all on); l0_relu, when given, replaces relu[0] (ptt_sa_desc.l0_relu is layer 0's flag once that layer is hoisted).
+    A float32 run divides by `radius` as torch divides a float32 tensor by a host scalar; the float64 run by its .double()."""
+    cast = (lambda t: t.double()) if dtype == torch.float64 else (lambda t: t.float())
+    x, c = cast(xyz), cast(new_xyz)
     g = _sa_gather64(x.transpose(1, 2).contiguous(), idx) - c.transpose(1, 2).unsqueeze(-1)
-    g = g / float(np.float32(radius))
+    if normalize_xyz:
+        g = g / (float(np.float32(radius)) if dtype == torch.float64 else radius)
     if feats is not None:
-        g = torch.cat([g, _sa_gather64(feats.double(), idx)], dim=1)
-    return F.max_pool2d(R.shared_mlp_eval(g, double_layers(layers)), kernel_size=[1, ns]).squeeze(-1)
+        f = _sa_gather64(cast(feats), idx)
+        g = torch.cat([g, f], dim=1) if use_xyz else f
+    elif not use_xyz:
+        raise ValueError("use_xyz = False without point features: nothing to group (pointnet2_utils.py:365-367)")
+    if relu is not None or l0_relu is not None:
+        relu = [True] * len(layers) if relu is None else list(relu)
+        if l0_relu is not None:
+            relu[0] = bool(l0_relu)
+    lay = double_layers(layers) if dtype == torch.float64 else layers
+    return F.max_pool2d(mlp_eval(g, lay, relu), kernel_size=[1, ns]).squeeze(-1)
+
+
+def sa_ref64(xyz, new_xyz, feats, idx, layers, radius, ns, use_xyz=True, normalize_xyz=True, relu=None, l0_relu=None):
+    """oracle.dense_ref.query_and_group (use_xyz, normalize_xyz) + shared_mlp_eval + max-pool in float64 on a fixed idx."""
+    return sa_ref(xyz, new_xyz, feats, idx, layers, radius, ns, use_xyz, normalize_xyz, relu, l0_relu, torch.float64)
 
 
 @functools.lru_cache(maxsize=None)
@@ -149,7 +189,171 @@ def sa_case(name):
     ref64 = sa_ref64(xyz, new_xyz, feats, idx, layers, radius, ns)
     return Case(name=name, B=B, N=N, M=M, C=C, spec=spec, radius=radius, ns=ns, scale_in_weights=siw, hoist=hoist, kernel=kernel,
                 compact=compact, xyz=xyz, new_xyz=new_xyz, feats=feats, layers=layers, idx=idx, ref32=ref32, ref64=ref64,
-                Y=yardstick(ref32, ref64))
+                Y=yardstick(ref32, ref64), use_xyz=True, normalize_xyz=True, relu=(True,) * (len(spec) - 1))
+
+
+# ------------------------------------------------------------------------------------------- set abstraction: the options
+# The 13 shapes of SA_CASES again, on clouds whose balls hold DISTINCT points, one option set each. sa_case's resampled clouds
+# (synth.frames with K_s = N / 2) fill most balls with the centre and copies of it: rel is mostly 0, and the reference hardly
+# moves when normalize_xyz is flipped or the xyz channels are dropped (tests/test_fused_ref_cpu.py measures what these do).
+def cube_clouds(seed, B, N):
+    """(B,N,3) float32, uniform in [0, 1)^3 (a double just below 1 that rounds to 1.0f is put back below 1). With B >= 3 cloud 1 is a copy of cloud 0 and the LAST cloud is all zero: the
+    repeated-index and every-point-in-every-ball edges of sa_case's clouds stay."""
+    s = np.minimum(np.random.RandomState(seed).uniform(0, 1, (B, N, 3)).astype(np.float32), np.nextafter(np.float32(1), np.float32(0)))
+    if B >= 3:
+        s[1] = s[0]
+        s[-1] = 0.0
+    return s
+
+
+# A layer's form, as pt_utils.Conv2d can be built and as ptt_sa_layer can describe it:
+#   "bn"    conv + BatchNorm                                scale, shift                  (scale folded: NULL, shift)
+#   "bn0"   conv + BatchNorm with running_mean = beta = 0   scale, shift = NULL           (scale folded: NULL, NULL)
+#   "bias"  conv with bias, bn=False                        scale = NULL, shift = the bias
+#   "none"  conv without bias, bn=False                     scale = NULL, shift = NULL
+FORMS = ("bn", "bn0", "bias", "none")
+
+# id -> (shape: a key of SA_CASES, the options that differ from sa_case's: use_xyz, normalize_xyz, relu (per SharedMLP layer),
+#        forms (per layer), scale_in_weights, radius, seed)
+SA_OPTION_CASES = {
+    # normalize_xyz = 0 on every kernel family
+    "norm0_lds4_111":      ("lds4_111", dict(normalize_xyz=False)),
+    "norm0_lds12_1035":    ("lds12_1035", dict(normalize_xyz=False)),
+    "norm0_wave32_5":      ("wave32_5", dict(normalize_xyz=False)),
+    "norm0_wave16_21":     ("wave16_21", dict(normalize_xyz=False)),
+    "norm0_stream_33":     ("stream_33", dict(normalize_xyz=False)),
+    "norm0_stream_1027":   ("stream_1027", dict(normalize_xyz=False)),
+    "norm0_fused32_33":    ("fused32_33", dict(normalize_xyz=False)),
+    # 257 feature channels next to 3 coordinates, and a third of the outputs belong to the all-zero cloud: at the shape's own
+    # radius and seed 7 the flip moves 20.2 % of the outputs, at this radius and seed 24.6 %
+    "norm0_fused16_21":    ("fused16_21", dict(normalize_xyz=False, radius=0.35, seed=11)),
+    "norm0_fused64_10":    ("fused64_10", dict(normalize_xyz=False)),
+    # use_xyz = 0: the rows are the C feature channels alone, layer 0 packed with rot = 0
+    "noxyz_wave16_18":     ("wave16_18", dict(use_xyz=False)),
+    "noxyz_fused32_33":    ("fused32_33", dict(use_xyz=False)),
+    "noxyz_fused16_21":    ("fused16_21", dict(use_xyz=False)),
+    "noxyz_fused64_10":    ("fused64_10", dict(use_xyz=False)),
+    # the last layer without ReLU: the pooled maximum may be negative. A maximum over many distinct rows seldom is: at the
+    # shapes' own radii 4 - 18 % of the outputs are negative on these clouds, so the radius is lowered (the rule of
+    # tests/test_fused_ref_cpu.py: a case that misses a condition changes its radius or seed) until 26 - 33 % are
+    "last0_lds4_1":        ("lds4_1", dict(relu=(True, True, False))),
+    "last0_wave16_18":     ("wave16_18", dict(relu=(True, False), radius=0.2)),
+    "last0_stream_1029":   ("stream_1029", dict(relu=(True, True, False), radius=0.2)),
+    "last0_fused32_33":    ("fused32_33", dict(relu=(True, True, False), radius=0.2)),
+    "last0_fused16_21":    ("fused16_21", dict(relu=(True, True, False), radius=0.2)),
+    "last0_fused64_10":    ("fused64_10", dict(relu=(True, False), radius=0.25)),
+    # an inner layer without ReLU: the lds shape must fall to the wave kernel for either of `p.L[0].relu && p.L[1].relu`
+    # (sa_lds_kernel has both activations built in), the stream shape to the fused kernel for `p.L[0].relu`; and the fused
+    # kernel with layer 0 inside, where the flag is the middle layer's
+    "inner0_lds4_111":     ("lds4_111", dict(relu=(False, True, True))),
+    "inner1_lds4_111":     ("lds4_111", dict(relu=(True, False, True))),
+    "inner1_lds12_1035":   ("lds12_1035", dict(relu=(True, False, True))),
+    "inner0_stream_33":    ("stream_33", dict(relu=(True, False, True))),
+    "inner1_fused32_33":   ("fused32_33", dict(relu=(True, False, True))),
+    # the hoisted layer 0 without ReLU (ptt_sa_desc.l0_relu = 0)
+    "l0relu0_stream_1027": ("stream_1027", dict(relu=(False, True, True))),
+    "l0relu0_fused16_21h": ("fused16_21h", dict(relu=(False, True, True))),
+    # shift = NULL and scale = NULL
+    "none_wave16_18":      ("wave16_18", dict(forms=("none", "none"))),
+    "none_fused16_21":     ("fused16_21", dict(forms=("none", "bias", "none"))),
+    "bn0_wave32_5":        ("wave32_5", dict(forms=("bn0", "bn0", "bn0"))),            # scale set, shift = NULL
+    "bn0_fused32_33":      ("fused32_33", dict(forms=("bn0", "bn", "bn0"))),
+    "bn0_lds4_1":          ("lds4_1", dict(forms=("bn0", "bn0", "bn0"))),              # scale folded, shift = NULL
+    "bn0_stream_33":       ("stream_33", dict(forms=("bn", "bn0", "bn0"))),
+}
+
+
+def option_layers(layers, forms, use_xyz):
+    """The layers of a shape in the forms of an option case: the same convolution weights (use_xyz off: without their three
+    xyz columns), BatchNorm kept, centred ("bn0") or replaced by a bias / by nothing."""
+    out = []
+    for l, (L, form) in enumerate(zip(layers, forms)):
+        assert form in FORMS
+        w = L["conv_weight"]
+        if l == 0 and not use_xyz:
+            w = w[:, 3:].contiguous()
+        if form in ("bn", "bn0"):
+            n = dict(L, conv_weight=w)
+            if form == "bn0":
+                n.update(bn_mean=torch.zeros_like(L["bn_mean"]), bn_bias=torch.zeros_like(L["bn_bias"]), shift_is_zero=True)
+        else:
+            n = {"conv_weight": w}
+            if form == "bias":
+                n["conv_bias"] = L["bn_bias"].clone()
+        out.append(n)
+    return out
+
+
+def layer_affine(L):
+    """(scale | None, shift | None) with which a layer is (W x) * scale + shift, float32 on the host, formed as
+    tests.util.fold_layers forms them; shift is None where it is zero by construction (what a caller passes as NULL)."""
+    if "bn_weight" not in L:
+        return None, L.get("conv_bias")
+    scale = L["bn_weight"] / torch.sqrt(L["bn_var"] + L["eps"])
+    return scale, (None if L.get("shift_is_zero") else L["bn_bias"] - L["bn_mean"] * scale)
+
+
+def option_kernel(c):
+    """sa_dispatch for an (option) case: what the C dispatch sees of its flags."""
+    run = c.relu[1:] if c.hoist else c.relu
+    no_scale = c.scale_in_weights or all("bn_weight" not in L for L in (c.layers[1:] if c.hoist else c.layers))
+    return sa_dispatch(c.B, c.M, c.C, c.spec, c.ns, no_scale, c.hoist, c.use_xyz, run[0], run[1] if len(run) > 1 else True)
+
+
+def option_flips(c):
+    """The single flags an option case varies -> {name: keyword arguments of sa_ref with that ONE flag put back}."""
+    flips = {}
+    if not c.normalize_xyz:
+        flips["normalize_xyz"] = dict(normalize_xyz=True)
+    if not c.use_xyz:                                   # the xyz channels back, with the weight columns the case dropped
+        flips["use_xyz"] = dict(use_xyz=True, layers=c.layers_xyz)
+    for l, on in enumerate(c.relu):
+        if not on:
+            flips["relu[%d]" % l] = dict(relu=tuple(True if k == l else r for k, r in enumerate(c.relu)))
+    if "bn0" in c.forms and not c.scale_in_weights:     # a scale pointer next to shift = NULL: the scale ignored
+        flips["scale"] = dict(layers=[{"conv_weight": L["conv_weight"]} if f == "bn0" else L for L, f in zip(c.layers, c.forms)])
+    return flips
+
+
+def option_ref(c, dtype=torch.float64, **override):
+    kw = dict(use_xyz=c.use_xyz, normalize_xyz=c.normalize_xyz, relu=c.relu, layers=c.layers)
+    kw.update(override)
+    layers = kw.pop("layers")
+    return sa_ref(c.xyz, c.new_xyz, c.feats, c.idx, layers, c.radius, c.ns, dtype=dtype, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def sa_option_case(name):
+    shape, opt = SA_OPTION_CASES[name]
+    B, N, M, C, spec, radius, ns, siw, hoist, _, _ = SA_CASES[shape]
+    use_xyz, normalize = opt.get("use_xyz", True), opt.get("normalize_xyz", True)
+    relu = tuple(opt.get("relu", (True,) * (len(spec) - 1)))
+    forms = tuple(opt.get("forms", ("bn",) * (len(spec) - 1)))
+    radius, siw = opt.get("radius", radius), opt.get("scale_in_weights", siw)
+    assert len(relu) == len(forms) == len(spec) - 1 and (use_xyz or (C > 0 and not hoist))
+    rs = np.random.RandomState(N + C)
+    s = cube_clouds(opt.get("seed", 7), B, N)
+    xyz = torch.from_numpy(s)
+    inds = torch.from_numpy(O.fps(s, M))
+    new_xyz = torch.gather(xyz, 1, inds.long()[..., None].expand(-1, -1, 3)).contiguous()
+    feats = torch.from_numpy(rs.standard_normal((B, C, N)).astype(np.float32)) if C else None
+    layers = option_layers(mlp_layers(N, spec), forms, use_xyz)          # the shape's own weights
+    idx = torch.from_numpy(np.ascontiguousarray(O.ball_query(new_xyz.numpy(), s, radius, ns)))
+    spec = list(spec) if use_xyz else [C] + list(spec[1:])
+    c = Case(name=name, shape=shape, B=B, N=N, M=M, C=C, spec=spec, radius=radius, ns=ns, scale_in_weights=siw, hoist=hoist,
+             xyz=xyz, new_xyz=new_xyz, feats=feats, layers=layers, idx=idx, use_xyz=use_xyz, normalize_xyz=normalize, relu=relu,
+             forms=forms, layers_xyz=option_layers(mlp_layers(N, SA_CASES[shape][4]), forms, True))
+    c["kernel"], _ = option_kernel(c)
+    c["compact"] = c.kernel.startswith(("sa_lds", "sa_stream"))
+    c["ref32"], c["ref64"] = option_ref(c, torch.float32), option_ref(c)
+    c["Y"] = yardstick(c.ref32, c.ref64)
+    return c
+
+
+def distinct_full_share(c):
+    """Share of a case's balls whose ns slots hold ns distinct points."""
+    srt = np.sort(c.idx.numpy(), axis=-1)
+    return float(((srt[..., 1:] != srt[..., :-1]).sum(axis=-1) + 1 == c.ns).mean())
 
 
 # -------------------------------------------------------------------------------------------------------------------- xcorr

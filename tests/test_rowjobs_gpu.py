@@ -143,6 +143,18 @@ def test_bad_jobs_are_refused(dev):
 def test_sa_level_as_two_jobs(dev, B, N, M, ns, C):
     """A set-abstraction level with its first convolution hoisted (pointnet2_modules.py:57-90 on per-point terms): grouped
     layer 1 built in the A staging (term[idx] + Wx . rel, ReLU), layer 2 + max over the neighbours in the epilogue."""
+    _sa_level_as_two_jobs(dev, B, N, M, ns, C, True, True)
+
+
+def test_sa_level_as_two_jobs_without_normalize_and_prologue_relu(dev):
+    """Prologue 3 with both of its options off (rowjobs.hip: `J.normalize_xyz`, `J.pro_relu`): rel is not divided by the radius
+    and layer 0's output enters layer 1 without ReLU — the same float64 reference and bounds as the case above. The
+    relative coordinates are 3.3 x smaller than normalised ones and half of layer 0's outputs are negative, so either
+    option ignored moves the result far outside the bound."""
+    _sa_level_as_two_jobs(dev, 2, 100, 33, 16, 256, False, False)
+
+
+def _sa_level_as_two_jobs(dev, B, N, M, ns, C, normalize, pro_relu):
     rs = np.random.RandomState(B * 1000 + M)
     xyz = rs.uniform(-1, 1, (B, N, 3)).astype(np.float32)
     centres = xyz[:, :M].copy()
@@ -154,14 +166,15 @@ def test_sa_level_as_two_jobs(dev, B, N, M, ns, C):
     radius = 0.3
     d = lambda a: torch.from_numpy(a).double()
     bi = np.arange(B)[:, None, None]
-    rel = (d(xyz)[bi, idx] - d(centres)[:, :, None, :]) / np.float32(radius)
-    a = (d(term)[bi, idx] + rel @ d(wx)).clamp_min(0)                          # (B,M,ns,C)
+    rel = (d(xyz)[bi, idx] - d(centres)[:, :, None, :]) / (np.float32(radius) if normalize else 1.0)
+    a = d(term)[bi, idx] + rel @ d(wx)                                         # (B,M,ns,C)
+    a = a.clamp_min(0) if pro_relu else a
     h = (a @ d(w1).t() + d(b1)).clamp_min(0)
     ref = (h @ d(w2).t() + d(b2)).max(dim=2)[0].clamp_min(0)                    # (B,M,256)
     hb = torch.empty((B * M * ns, 256), device=dev)
     ops.row_jobs([ops.row_job(ops.pack_weight(_t(w1, dev)), 256, prologue=3, x=_t(term, dev), idx=_t(idx, dev), xyz=_t(xyz, dev),
-                              centres=_t(centres, dev), wx=_t(wx, dev), radius=radius, ns=ns, M=M, N=N, normalize_xyz=True,
-                              pro_relu=True, shift=_t(b1, dev), act=1, out=hb)])
+                              centres=_t(centres, dev), wx=_t(wx, dev), radius=radius, ns=ns, M=M, N=N, normalize_xyz=normalize,
+                              pro_relu=pro_relu, shift=_t(b1, dev), act=1, out=hb)])
     np.testing.assert_allclose(hb.cpu().numpy(), h.reshape(-1, 256).numpy(), atol=2e-4, rtol=1e-4)
     out = torch.full((B, M, 256), float('nan'), device=dev)
     ops.row_jobs([ops.row_job(ops.pack_weight(_t(w2, dev)), 256, x=_t(h.reshape(-1, 256).float().numpy(), dev), epilogue=2, ns=ns, M=M,
