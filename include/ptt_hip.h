@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 36
+#define PTT_ABI_VERSION 37
 
 enum {
     PTT_OK = 0,
@@ -453,6 +453,45 @@ typedef struct ptt_attn_desc {
 } ptt_attn_desc;
 
 int ptt_pt_attn_pair_f32(const ptt_attn_desc* d, ptt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * Split-bf16 form of the single-head pair kernel (ABI 37; TransformerBlock.precision = 'bf16x2', off by default).
+ * Every fp32 operand x of the three D x D GEMMs (fc_delta[2], fc_gamma[0], fc_gamma[2]) is taken as two bf16 pieces,
+ *   hi = bf16(x) rounded to nearest even, lo = bf16(x - float(hi)),
+ * and a product is hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation. Everything else — rel rows,
+ * fc_delta[0], q | k | v, biases, softmax, the weighted sum, res and attn — is the fp32 kernel's.
+ *
+ * Split pack of a (Cout, K) fp32 weight W (row-major, W[col][k]), Cout % 32 == 0 and K % 16 == 0 (PTT_EINVAL otherwise):
+ * 2 * Cout * K bf16 elements (uint16 words), NT = Cout / 32. Element
+ *     e = (((kb * NT + ct) * 2 + piece) * 64 + lane) * 8 + j,   kb < K / 16, ct < NT, piece < 2, lane < 64, j < 8
+ * holds piece `piece` (0 = hi, 1 = lo) of W[32 * ct + (lane & 31)][16 * kb + 8 * (lane >> 5) + j]: the B-fragment order of
+ * v_mfma_f32_32x32x16_bf16, each lane's fragment of a (16-channel block, 32-column tile, piece) being one 16-byte load.
+ * ptt_split_weight_elems is a host call (no device work): the bf16 elements of one split pack, both pieces; 0 for sizes that
+ * are not positive. */
+int ptt_split_weight_elems(int Cout, int K);
+int ptt_pack_weight_split_bf16(const float* W, int Cout, int K, void* out, ptt_stream_t stream);
+
+/* ptt_attn_desc without `heads`: one head. The shape rules and refusals of ptt_pt_attn_pair_f32 for one head: D 128, 256, 512
+ * and k 8, 16, 32 are instantiated, N % (32 / k) == 0 and N >= k (PTT_EUNSUPPORTED otherwise). A refused launch writes nothing. */
+typedef struct ptt_attn_split_desc {
+    const float* xyz;      /* (B,N,3) */
+    const float* rel;      /* (B,N,k,3) from ptt_knn_rel_f32, or NULL */
+    const int32_t* knn;    /* (B,N,k) */
+    const float* qkv;      /* (B,N,3*D) fp32 */
+    const float* Wd1p;     /* the fp32 pack of ptt_attn_desc.Wd1p: fc_delta[0] stays one exact fp32 K-block */
+    const void* Wd2s;      /* split pack of fc_delta[2].weight */
+    const float* bd2;
+    const void* Wg1s;      /* split pack of fc_gamma[0].weight */
+    const float* bg1;
+    const void* Wg2s;      /* split pack of fc_gamma[2].weight */
+    const float* bg2;      /* accepted, never read (cancels in softmax_j) */
+    float* res;            /* (B,N,D) */
+    float* attn;           /* (B,N,k,D) or NULL */
+    int B, N, k, D;
+    const int32_t* order;  /* (B,N) from ptt_spatial_order_f32, or NULL; results do not depend on it */
+} ptt_attn_split_desc;
+
+int ptt_pt_attn_pair_split_f32(const ptt_attn_split_desc* d, ptt_stream_t stream);
 /* order (B,N) i32: the points of every cloud along a Morton curve through the cloud's bounding box (flat indices b*N + n,
  * ties by index: a permutation inside each cloud), N <= 8192. Neighbours in space become neighbours in launch order. */
 int ptt_spatial_order_f32(const float* xyz, int B, int N, int32_t* order, ptt_stream_t stream);

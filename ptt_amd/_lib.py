@@ -264,6 +264,15 @@ class AttnDesc(Structure):
                 ("B", c_int), ("N", c_int), ("k", c_int), ("D", c_int), ("order", c_void_p), ("heads", c_int)]
 
 
+class AttnSplitDesc(Structure):
+    """ptt_attn_split_desc: ptt_attn_desc without `heads`, Wd2s / Wg1s / Wg2s being split-bf16 packs."""
+    _fields_ = [("xyz", c_void_p), ("rel", c_void_p), ("knn", c_void_p), ("qkv", c_void_p),
+                ("Wd1p", c_void_p), ("Wd2s", c_void_p), ("bd2", c_void_p),
+                ("Wg1s", c_void_p), ("bg1", c_void_p), ("Wg2s", c_void_p), ("bg2", c_void_p),
+                ("res", c_void_p), ("attn", c_void_p),
+                ("B", c_int), ("N", c_int), ("k", c_int), ("D", c_int), ("order", c_void_p)]
+
+
 _lib = None
 
 

@@ -41,6 +41,11 @@ def _rows2d(layers, x):
 
 SPATIAL_ORDER_MIN_POINTS = 512       # clouds from this size on are handed to the pair kernel in Morton order
 FUSED_D_MODEL, FUSED_KNN = (128, 256, 512), (8, 16, 32)      # what ptt_pt_attn_pair_f32 instantiates for one head
+PRECISIONS = ('fp32', 'bf16x2')
+# the (d_model, k) at which precision 'bf16x2' runs the split-bf16 pair kernel (ptt_pt_attn_pair_split_f32). A pair at which
+# the split kernel is not faster than the fp32 one by more than the fp32 arm's own min-max spread is taken out here and runs
+# in fp32 with a note (DESIGN.md "Split-bf16 pair kernel", profiles/pair_split_timing.json); the kernel instantiation stays.
+SPLIT_DISPATCH = frozenset((D, k) for D in FUSED_D_MODEL for k in FUSED_KNN)
 
 
 class TransformerBlock(nn.Module):
@@ -57,6 +62,25 @@ class TransformerBlock(nn.Module):
         self.d_model = d_model
         self.d_points = d_points
         self._cache = ParamCache()
+        self._precision = 'fp32'
+
+    # ---------------------------------------------------------------- arithmetic of the fused pair kernel
+    @property
+    def precision(self):
+        """'fp32' (default) or 'bf16x2': the eval-mode pair kernel takes the operands of its three d_model x d_model GEMMs as
+        two bf16 pieces each (ptt_pt_attn_pair_split_f32). The one-frame forms and training stay fp32 either way."""
+        return getattr(self, '_precision', 'fp32')
+
+    @precision.setter
+    def precision(self, value):
+        if value not in PRECISIONS:
+            raise ValueError("TransformerBlock.precision must be one of %s, got %r" % (", ".join(map(repr, PRECISIONS)), value))
+        if value != self.precision:
+            self._cache.drop()          # the split packs exist only under 'bf16x2'; a captured graph addressed the old entry
+        self._precision = value
+
+    def _name(self):
+        return 'TransformerBlock(d_model=%d, k=%d)' % (self.d_model, self.k)
 
     # ---------------------------------------------------------------- fused-path parameters
     def _fusable(self, xyz, features):
@@ -89,7 +113,12 @@ class TransformerBlock(nn.Module):
         # fc1 has no activation and only feeds w_qs / w_ks / w_vs (variants.py:155-156), so the two linear maps
         # are one: [q|k|v] = (W_qkv W_1) f + W_qkv b_1 — 256 -> 1536 instead of 256 -> 512 -> 1536 (product in f64)
         wqkv = torch.cat([self.w_qs.weight, self.w_ks.weight, self.w_vs.weight], 0).double()
+        split = {}
+        if self.precision == 'bf16x2' and (self.d_model, self.k) in SPLIT_DISPATCH:       # only then: fp32 mode packs nothing new
+            split = dict(wd2s=ops.pack_weight_split(self.fc_delta[2].weight), wg1s=ops.pack_weight_split(self.fc_gamma[0].weight),
+                         wg2s=ops.pack_weight_split(self.fc_gamma[2].weight))
         return dict(
+            split,
             qkv=ops.pack_weight((wqkv @ self.fc1.weight.double()).float().contiguous()),
             qkv_b=(wqkv @ self.fc1.bias.double()).float().contiguous(),
             wd1=ops.pack_delta0(self.fc_delta[0].weight, self.fc_delta[0].bias),
@@ -116,6 +145,12 @@ class TransformerBlock(nn.Module):
                 knn_idx, rel = ops.knn(xyz, self.k, want_rel=True)
             # the per-layer forms below have 16 neighbours and the 512-wide layout built in (rowjobs.hip, prologue 2 / epilogue 1)
             per_layer = (D, self.k) == (512, 16) and xyz.shape[0] * xyz.shape[1] <= PER_LAYER_MAX_POINTS
+            split = self.precision == 'bf16x2'
+            if split and per_layer:
+                ops.note_precision_fallback(self._name(), 'at most %d points: the one-frame per-layer forms are fp32 only' % PER_LAYER_MAX_POINTS)
+            elif split and 'wd2s' not in P:
+                split = False
+                ops.note_precision_fallback(self._name(), 'the split-bf16 pair kernel is not faster at this (d_model, k): not dispatched')
             if per_layer and not want_attn:
                 # a handful of frames (one tracklet frame: 128 / 64 points): the fused pair kernel's one workgroup per two
                 # points is a 64-workgroup launch of three chained 512 x 512 GEMMs (106 us on 64 of the 256 CUs). Per layer,
@@ -157,8 +192,12 @@ class TransformerBlock(nn.Module):
                 # gather k | v rows of the same neighbourhood out of L2 (FPS order = far apart: ~10x the compulsory HBM reads
                 # at 2048 points); the k | v rows of a 128-point cloud fit L2 whole
                 order = ops.spatial_order(xyz) if SPATIAL_ORDER_MIN_POINTS <= xyz.shape[1] <= 8192 else None
-                res, attn = ops.pt_attn_pair(xyz, knn_idx, qkv, P['wd1'], P['wd2'], P['bd2'], P['wg1'],
-                                             P['bg1'], P['wg2'], P['bg2'], D, want_attn, rel=rel, order=order)
+                if split:
+                    res, attn = ops.pt_attn_pair_split(xyz, knn_idx, qkv, P['wd1'], P['wd2s'], P['bd2'], P['wg1s'],
+                                                       P['bg1'], P['wg2s'], P['bg2'], D, want_attn, rel=rel, order=order)
+                else:
+                    res, attn = ops.pt_attn_pair(xyz, knn_idx, qkv, P['wd1'], P['wd2'], P['bd2'], P['wg1'],
+                                                 P['bg1'], P['wg2'], P['bg2'], D, want_attn, rel=rel, order=order)
             res = ops.linear(res, P['fc2'], self.d_points, None, P['fc2_b'], False, features)
             return res, attn
 
@@ -168,6 +207,8 @@ class TransformerBlock(nn.Module):
             # _AttnAggregate); the neighbour gathers of k and v happen inside those passes and their gradients come back
             # through the deterministic row scatter-add. kNN: the HIP kernel (ascending (distance, index), a stable
             # refinement of the reference's argsort).
+            if self.precision == 'bf16x2':
+                ops.note_precision_fallback(self._name(), 'training runs in fp32')
             knn_idx, rel = ops.knn(xyz.contiguous(), self.k, want_rel=True)          # rel = xyz_i - xyz_j (:158)
             if xyz.requires_grad:                                                     # the box head's proposals carry grad
                 rel = train_ops._KnnRel.apply(xyz, knn_idx, rel)

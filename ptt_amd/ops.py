@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, SaDesc, SaLayer, XcorrDesc
+from ._lib import AttnDesc, AttnSplitDesc, SaDesc, SaLayer, XcorrDesc
 
 
 def _stream():
@@ -87,6 +87,22 @@ def note_unfused(name, reason):
         warnings.warn("ptt_amd: %s runs on stock torch ops, not the fused HIP kernels: %s" % (name, reason),
                       RuntimeWarning, stacklevel=3)
     return False
+
+
+# A module whose precision is 'bf16x2' runs the split-bf16 pair kernel where it is dispatched; a call that stays on the fp32
+# kernels under that setting (the one-frame forms, training, a shape taken out of the dispatch) is counted here and said once
+# per reason. Not in unfused_calls: these calls still run the hand-written kernels.
+precision_fallbacks = {}    # (module name, reason) -> number of calls under precision 'bf16x2' that ran in fp32
+
+
+def note_precision_fallback(name, reason):
+    key = (name, reason)
+    n = precision_fallbacks.get(key, 0)
+    precision_fallbacks[key] = n + 1
+    if n == 0:
+        import warnings
+        warnings.warn("ptt_amd: %s has precision 'bf16x2' but this call runs the fp32 kernels: %s" % (name, reason),
+                      RuntimeWarning, stacklevel=3)
 
 
 param_generation = 0        # bumped whenever a module replaces or drops a cached set of packed / folded parameters
@@ -418,6 +434,20 @@ def pack_weight(weight, rot=0):
     return out
 
 
+def pack_weight_split(weight):
+    """(Cout,K) f32, Cout % 32 == 0 and K % 16 == 0 -> the split-bf16 pack ptt_pt_attn_pair_split_f32 reads (1-D int16 tensor of
+    2 * Cout * K bf16 words: hi and lo pieces in MFMA B-fragment order, include/ptt_hip.h)."""
+    w = weight.detach()
+    w = w.reshape(w.shape[0], -1).contiguous().float()
+    _chk(w, "weight", torch.float32, 2)
+    Cout, K = w.shape
+    if Cout % 32 != 0 or K % 16 != 0:
+        raise ValueError("pack_weight_split: Cout=%d must be a multiple of 32 and K=%d a multiple of 16" % (Cout, K))
+    out = torch.empty((_host("ptt_split_weight_elems", Cout, K),), dtype=torch.int16, device=w.device)
+    _launch("ptt_pack_weight_split_bf16", w.device, _ptr(w), Cout, K, _ptr(out))
+    return out
+
+
 ONE_FRAME_MAX_SA_ROWS = 4096   # (= 4 frames of vote_aggregation, the batch range of ONE_FRAME_MAX_POINTS) grouped rows (B * npoint * nsample) up to which a hoisted SA level runs as two row-job launches
 ROW_JOB_MAX_ROWS = 1024       # ops.linear hands launches of at most this many rows (and K >= 192) to ptt_row_jobs_f32
 ONE_FRAME_MAX_POINTS = int(os.environ.get("PTT_PT_PER_LAYER_MAX", "512"))   # B * N up to which the modules take the one-frame launch chain
@@ -704,6 +734,44 @@ def pt_attn_pair(xyz, knn_idx, qkv, wd1p, wd2p, bd2, wg1p, bg1, wg2p, bg2, d_mod
             raise ValueError("order: (B,N) int32 expected")
         d.order = order.data_ptr()
     _launch("ptt_pt_attn_pair_f32", xyz.device, ctypes.byref(d), timed='ptt_pt_attn_pair_f32')
+    return res, attn
+
+
+def pt_attn_pair_split(xyz, knn_idx, qkv, wd1p, wd2s, bd2, wg1s, bg1, wg2s, bg2, d_model, want_attn=True, rel=None, order=None):
+    """pt_attn_pair for one head in split-bf16 arithmetic (ptt_pt_attn_pair_split_f32): the three d_model x d_model GEMMs take
+    every operand as two bf16 pieces (hi.hi + hi.lo + lo.hi, fp32 accumulation), everything else is pt_attn_pair's.
+    wd1p = pack_delta0(...) as there; wd2s / wg1s / wg2s from pack_weight_split. Same shapes, same refusals, same returns."""
+    _chk(xyz, "xyz", torch.float32, 3)
+    _chk(knn_idx, "knn_idx", torch.int32, 3)
+    _chk(qkv, "qkv", torch.float32, 3)
+    B, N, _ = xyz.shape
+    k = knn_idx.shape[2]
+    D = int(d_model)
+    if not pair_heads_supported(D, k, 1):
+        raise ValueError("pt_attn_pair_split: d_model=%d k=%d (%s)" % (D, k, PAIR_ENVELOPE))
+    if N % (32 // k) != 0 or N < k:
+        raise ValueError("pt_attn_pair_split: N=%d must be a multiple of %d (the points of a 32-row tile) and >= k=%d" % (N, 32 // k, k))
+    if tuple(knn_idx.shape[:2]) != (B, N) or tuple(qkv.shape) != (B, N, 3 * D):
+        raise ValueError("pt_attn_pair_split: knn_idx (B,N,k) and qkv (B,N,3*d_model) expected")
+    for name, t in (("wd2s", wd2s), ("wg1s", wg1s), ("wg2s", wg2s)):
+        if t.dtype != torch.int16 or t.numel() != 2 * D * D or not t.is_cuda:
+            raise ValueError("pt_attn_pair_split: %s must be pack_weight_split of a (%d,%d) weight" % (name, D, D))
+    res = torch.empty((B, N, D), dtype=torch.float32, device=xyz.device)
+    attn = torch.empty((B, N, k, D), dtype=torch.float32, device=xyz.device) if want_attn else None
+    d = AttnSplitDesc()
+    d.xyz, d.knn, d.qkv = xyz.data_ptr(), knn_idx.data_ptr(), qkv.data_ptr()
+    d.rel = rel.data_ptr() if rel is not None else None
+    d.Wd1p, d.Wd2s, d.bd2 = wd1p.data_ptr(), wd2s.data_ptr(), bd2.data_ptr()
+    d.Wg1s, d.bg1, d.Wg2s, d.bg2 = wg1s.data_ptr(), bg1.data_ptr(), wg2s.data_ptr(), bg2.data_ptr()
+    d.res = res.data_ptr()
+    d.attn = attn.data_ptr() if attn is not None else None
+    d.B, d.N, d.k, d.D = B, N, k, D
+    if order is not None:
+        _chk(order, "order", torch.int32, 2)
+        if tuple(order.shape) != (B, N):
+            raise ValueError("order: (B,N) int32 expected")
+        d.order = order.data_ptr()
+    _launch("ptt_pt_attn_pair_split_f32", xyz.device, ctypes.byref(d), timed='ptt_pt_attn_pair_split_f32')
     return res, attn
 
 
