@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 37
+#define PTT_ABI_VERSION 38
 
 enum {
     PTT_OK = 0,
@@ -492,6 +492,39 @@ typedef struct ptt_attn_split_desc {
 } ptt_attn_split_desc;
 
 int ptt_pt_attn_pair_split_f32(const ptt_attn_split_desc* d, ptt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * Split-bf16 form of the streamed set-abstraction level (ABI 38; PointnetSAModuleVotes.precision = 'bf16x2', off by default).
+ * One shape, the one ptt_sa_fused_fwd_f32 hands to its streamed kernel: a hoisted layer 0 with 128 channels, kernel layer 1
+ * 128 -> 128 with ReLU, kernel layer 2 128 -> 256 (ReLU when relu2 != 0), 32 neighbours, the BatchNorm scale folded into the
+ * weights, fp32 shifts. h0 = act(l0_point_term[idx] + l0_xyz_weight . rel) is formed in fp32 exactly as ptt_sa_fused_fwd_f32
+ * forms it (the normalize_xyz divide, the l0_relu floor), then split into hi = bf16(x) (round to nearest even) and
+ * lo = bf16(x - float(hi)); each layer takes hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, the
+ * shifts, the ReLUs and the max over the 32 neighbours run in fp32 (h1 is split again before layer 2), the store is fp32.
+ * W1s / W2s: ptt_pack_weight_split_bf16 of the (128,128) and (256,128) weights with the scale folded in. shift1 / shift2 may
+ * be NULL (no shift). B == 0 or M == 0: PTT_OK, nothing is launched. A NULL pointer among the others: PTT_EINVAL;
+ * l0_point_term, l0_xyz_weight, W1s or W2s not 16-byte aligned, or a negative output stride: PTT_EINVAL; an array of the
+ * launch over 2 GiB (32-bit offsets): PTT_EUNSUPPORTED. A refused call writes nothing. */
+typedef struct ptt_sa_split_desc {
+    const float* xyz;            /* (B,N,3) */
+    const float* new_xyz;        /* (B,M,3) */
+    const int32_t* idx;          /* (B,M,32) neighbour indices in [0,N) */
+    const float* l0_point_term;  /* (B,N,128): layer 0's feature half per point, shift included */
+    const float* l0_xyz_weight;  /* (3,128): layer 0's coordinate columns, transposed, scale folded */
+    int l0_relu;                 /* layer 0's ReLU */
+    const void* W1s;             /* split pack, Cout = 128, K = 128 */
+    const float* shift1;         /* (128) or NULL */
+    const void* W2s;             /* split pack, Cout = 256, K = 128 */
+    const float* shift2;         /* (256) or NULL */
+    int relu2;                   /* layer 2's ReLU (after the max, which commutes with it) */
+    float* out;                  /* element (b, c, m) at out[b*out_sb + c*out_sc + m*out_sm] */
+    long long out_sb, out_sc, out_sm;
+    int B, N, M;
+    float radius;
+    int normalize_xyz;
+} ptt_sa_split_desc;
+
+int ptt_sa_stream_split_f32(const ptt_sa_split_desc* d, ptt_stream_t stream);
 /* order (B,N) i32: the points of every cloud along a Morton curve through the cloud's bounding box (flat indices b*N + n,
  * ties by index: a permutation inside each cloud), N <= 8192. Neighbours in space become neighbours in launch order. */
 int ptt_spatial_order_f32(const float* xyz, int B, int N, int32_t* order, ptt_stream_t stream);

@@ -273,6 +273,15 @@ class AttnSplitDesc(Structure):
                 ("B", c_int), ("N", c_int), ("k", c_int), ("D", c_int), ("order", c_void_p)]
 
 
+class SaSplitDesc(Structure):
+    """ptt_sa_split_desc: the dense SA1 / SA2 stream level in split-bf16 arithmetic (W1s / W2s are split-bf16 packs)."""
+    _fields_ = [("xyz", c_void_p), ("new_xyz", c_void_p), ("idx", c_void_p),
+                ("l0_point_term", c_void_p), ("l0_xyz_weight", c_void_p), ("l0_relu", c_int),
+                ("W1s", c_void_p), ("shift1", c_void_p), ("W2s", c_void_p), ("shift2", c_void_p), ("relu2", c_int),
+                ("out", c_void_p), ("out_sb", c_longlong), ("out_sc", c_longlong), ("out_sm", c_longlong),
+                ("B", c_int), ("N", c_int), ("M", c_int), ("radius", c_float), ("normalize_xyz", c_int)]
+
+
 _lib = None
 
 

@@ -43,6 +43,16 @@ STREAM_COMPACT_MIN_BALLS = 2048
 # -> 23.75 / 23.76 ms (+2.8 %, two lines each, same session; spread 0.03 ms), although the launch alone costs the same
 # (1539 dense / 1532 compact us). Every car / ped / train level has at most 512 points.
 STREAM_COMPACT_MAX_POINTS = 1024
+PRECISIONS = ('fp32', 'bf16x2')
+# Fewest balls (B * M) of a launch that precision 'bf16x2' sends to the split-bf16 stream kernel (ptt_sa_stream_split_f32).
+# The rule is the pair kernel's (transformer_block/variants.py, SPLIT_DISPATCH): the split kernel is dispatched only where
+# scripts/sa_split_timing.py shows it faster than sa_stream_kernel<32> by more than the fp32 arm's own spread; a launch below
+# this count runs in fp32 with a note. Measured (kernel launch alone, us, fp32 / split; fp32 arm's min - max spread in brackets):
+#   balls   256 (one frame, 512 -> 256)   3072 (48 x 64)     6144 (48 x 128)     12288 (48 x 256)    131072 (stress)
+#           19.7 / 12.6 [0.4]             84.4 / 35.0 [6.4]  160.2 / 60.7 [16]   312.9 / 113.3 [39]  3079 / 1217 [21]
+# The split kernel wins at every count by many spreads, so the threshold is 0: every dense stream launch is dispatched
+# (DESIGN.md "Split-bf16 stream kernel", profiles/sa_split_timing.json).
+SPLIT_STREAM_MIN_BALLS = 0
 
 
 class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
@@ -65,8 +75,60 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
         self.mlp_module = pt_utils.SharedMLP(mlp_spec, bn=bn)
         self.sample_method = sample_method
         self._fused_cache = ParamCache()
+        self._split_cache = ParamCache()   # the split-bf16 packs of layers 1 and 2: built only under precision 'bf16x2'
+        self._precision = 'fp32'
         self.centres_knn_k = 0      # > 0: a caller that runs a TransformerBlock on this level's centres (the box head) wants their
         self.centres_knn = None     #      kNN; at one frame it is formed in the sampling launch and left here (knn_idx, rel)
+
+    # ------------------------------------------------------------------ arithmetic of the dense stream level
+    @property
+    def precision(self):
+        """'fp32' (default) or 'bf16x2': an eval-mode call that would reach the dense streamed kernel (hoisted 128-channel layer 0,
+        128 -> 128 -> 256, 32 neighbours) takes the operands of its two GEMMs as two bf16 pieces each (ptt_sa_stream_split_f32).
+        Every other call — SA0, a compact-gated level, the one-frame forms, other widths, training — stays fp32 either way."""
+        return getattr(self, '_precision', 'fp32')
+
+    @precision.setter
+    def precision(self, value):
+        if value not in PRECISIONS:
+            raise ValueError("PointnetSAModuleVotes.precision must be one of %s, got %r" % (", ".join(map(repr, PRECISIONS)), value))
+        if value != self.precision:
+            self._fused_cache.drop()    # a captured graph addressed the old mode's buffers
+            self._split_cache.drop()    # the split packs exist only under 'bf16x2'
+        self._precision = value
+
+    def _name(self):
+        return 'PointnetSAModuleVotes(nsample=%s, mlp=%s)' % (self.nsample, [u.conv.weight.shape[0] for u in self.mlp_module
+                                                                           if hasattr(u, 'conv')])
+
+    def _split_params(self, device):
+        """-> dict(w1s, shift1, w2s, shift2, relu2): layers 1 and 2 of the SharedMLP for ops.sa_stream_split — the BatchNorm scale
+        folded into the weights in float32 (the values the fp32 pack holds), then ops.pack_weight_split."""
+        return self._split_cache.get(conv_bn_tensors(self.mlp_module), device, self._fold_split)
+
+    def _fold_split(self):
+        packs = []
+        for unit in (self.mlp_module[1], self.mlp_module[2]):
+            scale, shift = fold_conv_bn(unit)
+            w = unit.conv.weight
+            wq = w if scale is None else w * scale.view(-1, 1, 1, 1)
+            packs.append((ops.pack_weight_split(wq), shift))
+        return dict(w1s=packs[0][0], shift1=packs[0][1], w2s=packs[1][0], shift2=packs[1][1],
+                    relu2=hasattr(self.mlp_module[2], 'activation'))
+
+    def _split_reason(self, features, hoist, layers, B, M, compact_gated):
+        """None when this eval-mode call runs the split-bf16 stream kernel, else why it stays on the fp32 kernels."""
+        if features is None:
+            return 'no point features (SA0): sa_lds_kernel is fp32 only'
+        if (hoist is None or hoist[2] != 128 or self.nsample != 32 or len(layers) != 3
+                or (layers[1].cin, layers[1].cout, layers[2].cin, layers[2].cout) != (128, 128, 128, 256) or not layers[1].relu
+                or layers[1].scale is not None or layers[2].scale is not None):
+            return 'other widths than a hoisted 128-channel layer 0, 128 -> 128 -> 256 and 32 neighbours: fp32 only'
+        if compact_gated:
+            return 'compact-gated level: sa_stream_compact_kernel is fp32 only'
+        if B * M < SPLIT_STREAM_MIN_BALLS:
+            return 'fewer than %d balls: the split-bf16 stream kernel is not faster there, not dispatched' % SPLIT_STREAM_MIN_BALLS
+        return None
 
     # ------------------------------------------------------------------ sampling (reference :63-77)
     def _sample(self, xyz, features, npoint):
@@ -91,8 +153,7 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
         says so once (ops.note_unfused)."""
         if self.training or not xyz.is_cuda:
             return False
-        name = 'PointnetSAModuleVotes(nsample=%s, mlp=%s)' % (self.nsample, [u.conv.weight.shape[0] for u in self.mlp_module
-                                                                              if hasattr(u, 'conv')])
+        name = self._name()
         if ops.autograd_recording(self, xyz, features):
             return ops.note_unfused(name, 'autograd is recording (wrap inference in torch.no_grad())')
         if self.sample_uniformly or self.nsample not in (16, 32, 64):
@@ -151,6 +212,8 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
         self.centres_knn = None
         if self._fusable(xyz, features):
             return self._forward_fused(xyz, features, npoint, inds, pre, compact)
+        if self.precision == 'bf16x2' and xyz.is_cuda:
+            ops.note_precision_fallback(self._name(), 'training (and every call the fused eval path turns away) runs in fp32')
         return self._forward_train(xyz, features, npoint, inds)
 
     def _forward_fused(self, xyz, features, npoint, inds, pre, compact):
@@ -183,6 +246,9 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
         else:
             new_xyz, inds64, idx = ops.centres_ball_query(xyz, inds.contiguous(), npoint, self.radius, self.nsample)
         layers, hoist = self._fused_params(xyz.device)
+        split = self.precision == 'bf16x2'
+        if split and (hoist is None or features is None):
+            ops.note_precision_fallback(self._name(), self._split_reason(features, hoist, layers, xyz.shape[0], npoint, False))
         if hoist is not None and features is not None:
             wf_packed, wx, c0, relu0 = hoist
             rows = features.transpose(1, 2)                       # (B,N,C): contiguous when point-major
@@ -195,6 +261,8 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
                 # kernel would be 16 workgroups with two chained 256 x 256 layers each (41 us); as two row-job launches
                 # the 1024 grouped rows spread over the chip: layer 1 on rows built while its A tile is staged (term[idx]
                 # + Wx . rel, ReLU), then layer 2 with the max over the neighbours as its epilogue
+                if split:
+                    ops.note_precision_fallback(self._name(), 'a handful of frames: the one-frame row-job forms are fp32 only')
                 L1, L2 = layers[1], layers[2]
                 h = torch.empty((B * M * ns, L1.cout), dtype=torch.float32, device=xyz.device)
                 ops.row_jobs([pt_utils.layer_job(L1, prologue=3, x=term, idx=idx, xyz=xyz, centres=new_xyz, wx=wx,
@@ -203,10 +271,18 @@ class PointnetSAModuleVotes(DropsCachesOnModeChange, nn.Module):
                 pooled = torch.empty((B, M, L2.cout), dtype=torch.float32, device=xyz.device)
                 ops.row_jobs([pt_utils.layer_job(L2, x=h, epilogue=2, ns=ns, M=M, out=pooled)])
                 return new_xyz, pooled.transpose(1, 2), inds64
+            compact_gated = bool(compact) and B * M >= STREAM_COMPACT_MIN_BALLS and xyz.shape[1] <= STREAM_COMPACT_MAX_POINTS
+            if split:
+                reason = self._split_reason(features, hoist, layers, B, M, compact_gated)
+                if reason is None:
+                    S = self._split_params(xyz.device)
+                    new_features = ops.sa_stream_split(xyz, new_xyz, idx, (term, wx, relu0), S['w1s'], S['shift1'], S['w2s'],
+                                                       S['shift2'], self.radius, self.normalize_xyz, relu2=S['relu2'])
+                    return new_xyz, new_features, inds64
+                ops.note_precision_fallback(self._name(), reason)
             new_features = ops.sa_fused_forward(xyz, new_xyz, idx, None, layers[1:], self.radius, True,
                                                 self.normalize_xyz, point_major_out=True, l0=(term, wx, relu0),
-                                                compact=(bool(compact) and B * M >= STREAM_COMPACT_MIN_BALLS
-                                                         and xyz.shape[1] <= STREAM_COMPACT_MAX_POINTS))
+                                                compact=compact_gated)
         else:
             # the level without point features (SA0) pools each ball's distinct rows only: same bits, a fraction of
             # the rows (ball-query padding and the resampled clouds' repeated points)

@@ -33,6 +33,8 @@ class PointNet2BackboneLight(nn.Module):
                 radius=sa.RADIUS[k], nsample=sa.NSAMPLE[k], mlp=mlps,
                 use_xyz=sa.get('USE_XYZ', True), normalize_xyz=sa.get('NORMALIZE_XYZ', True),
                 sample_method=sa.SAMPLE_METHOD[k]))
+            # optional PRECISION: 'fp32' (absent) or 'bf16x2', the split-bf16 stream kernel of the dense SA1 / SA2 levels
+            self.SA_modules[-1].precision = sa.get('PRECISION', 'fp32')
         self.cov_final = nn.Conv1d(256, 256, kernel_size=1)
         self.num_point_features = sa.MLPS[-1][-1]
         self._cov_cache = ParamCache()

@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, AttnSplitDesc, SaDesc, SaLayer, XcorrDesc
+from ._lib import AttnDesc, AttnSplitDesc, SaDesc, SaLayer, SaSplitDesc, XcorrDesc
 
 
 def _stream():
@@ -562,6 +562,56 @@ def sa_fused_forward(xyz, new_xyz, idx, features, layers, radius, use_xyz=True, 
         ws, (_, d.compact_ws_bytes) = _workspace("ptt_sa_compact_workspace", xyz.device, B, M)
         d.compact_ws = ws.data_ptr()
     _launch("ptt_sa_fused_fwd_f32", xyz.device, ctypes.byref(d), timed='ptt_sa_fused_fwd_f32')
+    return out
+
+
+def sa_stream_split(xyz, new_xyz, idx, l0, w1s, shift1, w2s, shift2, radius, normalize_xyz=False, relu2=True, point_major_out=True,
+                    out=None):
+    """The dense SA1 / SA2 stream level of sa_fused_forward in split-bf16 arithmetic (ptt_sa_stream_split_f32): a hoisted
+    128-channel layer 0, then 128 -> 128 (ReLU) -> 256, 32 neighbours. h0 is formed in fp32 as there; both layers take every
+    operand as two bf16 pieces (hi.hi + hi.lo + lo.hi, fp32 accumulation); shifts, ReLUs, the max and the store are fp32.
+    xyz (B,N,3), new_xyz (B,M,3), idx (B,M,32) i32; l0 = (point_term (B,N,128) contiguous, xyz_weight (3,128), relu);
+    w1s / w2s = pack_weight_split of the (128,128) / (256,128) weights with the BatchNorm scale folded in; shift1 (128) /
+    shift2 (256) float32 or None. out: an optional (B,256,M) float32 view to write (any non-negative strides).
+    Returns (B,256,M); with point_major_out it is a transposed view of (B,M,256) storage."""
+    _chk(xyz, "xyz", torch.float32, 3)
+    _chk(new_xyz, "new_xyz", torch.float32, 3)
+    _chk(idx, "idx", torch.int32, 3)
+    B, N, _ = xyz.shape
+    _, M, ns = idx.shape
+    term, wx, l0_relu = l0
+    _chk(term, "l0 point term", torch.float32, 3)
+    _chk(wx, "l0 xyz weight", torch.float32, 2)
+    if ns != 32 or tuple(term.shape) != (B, N, 128) or tuple(wx.shape) != (3, 128) or tuple(new_xyz.shape) != (B, M, 3):
+        raise ValueError("sa_stream_split: 32 neighbours, an l0 point term of (B,N,128) and an xyz weight of (3,128) expected "
+                         "(got nsample=%d, term %s, xyz weight %s)" % (ns, tuple(term.shape), tuple(wx.shape)))
+    for name, t, cout in (("w1s", w1s, 128), ("w2s", w2s, 256)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int16 or t.numel() != 2 * cout * 128 or not t.is_cuda:
+            raise ValueError("sa_stream_split: %s must be pack_weight_split of a (%d,128) weight" % (name, cout))
+    for name, t, cout in (("shift1", shift1, 128), ("shift2", shift2, 256)):
+        if t is not None:
+            _chk(t, name, torch.float32, 1)
+            if t.numel() != cout:
+                raise ValueError("sa_stream_split: %s must have %d elements" % (name, cout))
+    if out is None:
+        if point_major_out:
+            out = torch.empty((B, M, 256), dtype=torch.float32, device=xyz.device).transpose(1, 2)
+        else:
+            out = torch.empty((B, 256, M), dtype=torch.float32, device=xyz.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, 256, M):
+        raise ValueError("sa_stream_split: out must be a (B,256,M) float32 device tensor")
+    d = SaSplitDesc()
+    d.xyz, d.new_xyz, d.idx = xyz.data_ptr(), new_xyz.data_ptr(), idx.data_ptr()
+    d.l0_point_term, d.l0_xyz_weight, d.l0_relu = term.data_ptr(), wx.data_ptr(), int(bool(l0_relu))
+    d.W1s, d.W2s = w1s.data_ptr(), w2s.data_ptr()
+    d.shift1 = shift1.data_ptr() if shift1 is not None else None
+    d.shift2 = shift2.data_ptr() if shift2 is not None else None
+    d.relu2 = int(bool(relu2))
+    d.out = out.data_ptr()
+    d.out_sb, d.out_sc, d.out_sm = out.stride()
+    d.B, d.N, d.M = B, N, M
+    d.radius, d.normalize_xyz = float(radius), int(bool(normalize_xyz))
+    _launch("ptt_sa_stream_split_f32", xyz.device, ctypes.byref(d), timed='ptt_sa_stream_split_f32')
     return out
 
 
