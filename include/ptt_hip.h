@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define PTT_ABI_VERSION 38
+#define PTT_ABI_VERSION 39
 
 enum {
     PTT_OK = 0,
@@ -525,6 +525,36 @@ typedef struct ptt_sa_split_desc {
 } ptt_sa_split_desc;
 
 int ptt_sa_stream_split_f32(const ptt_sa_split_desc* d, ptt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * Split-bf16 form of the fused CosineSimAug kernel (ABI 39; CosineSimAug.precision = 'bf16x2', off by default).
+ * One shape, the shipped configuration's MLP.CHANNELS = [260, 256, 256, 256] on the batched form of ptt_xcorr_fused_fwd_f32
+ * (cos_t given, no split): C0 = 256 with the BatchNorm of layer 0 folded into P and w_sim, kernel layer 1 256 -> 256 with ReLU,
+ * kernel layer 2 256 -> 256 (ReLU when relu2 != 0), the BatchNorm scale folded into the weights, fp32 shifts, Nt % 64 == 0
+ * walked in chunks of 64 with a running max. h0 = max(P[b,i,:] + w_sim * cos_t[b,j,i], 0) is formed in fp32 exactly as
+ * ptt_xcorr_fused_fwd_f32 forms it, then split into hi = bf16(x) (round to nearest even) and lo = bf16(x - float(hi)); each
+ * layer takes hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, the shifts, layer 1's ReLU, the max over
+ * the template points and the ReLU after it run in fp32 (h1 is split again before layer 2), the store is fp32. There is no
+ * sim_out. W1s / W2s: ptt_pack_weight_split_bf16 of the two (256,256) weights with the scale folded in. shift1 / shift2 may be
+ * NULL (no shift). B == 0 or Ns == 0: PTT_OK, nothing is launched. A NULL descriptor or a NULL pointer among cos_t, P, w_sim,
+ * W1s, W2s, out: PTT_EINVAL; P, w_sim, W1s or W2s not 16-byte aligned, or a negative output stride: PTT_EINVAL; Nt <= 0 or
+ * Nt % 64 != 0: PTT_EUNSUPPORTED; an array of the launch over 2 GiB (32-bit offsets): PTT_EUNSUPPORTED. A refused call writes
+ * nothing. */
+typedef struct ptt_xcorr_split_desc {
+    const float* cos_t;          /* (B,Ns,Nt) from ptt_cosine_map_f32 */
+    const float* P;              /* (B,Nt,256) contiguous: layer 0's per-template-point term, BatchNorm folded in */
+    const float* w_sim;          /* (256): layer 0's similarity column, scale folded */
+    const void* W1s;             /* split pack, Cout = 256, K = 256 */
+    const float* shift1;         /* (256) or NULL */
+    const void* W2s;             /* split pack, Cout = 256, K = 256 */
+    const float* shift2;         /* (256) or NULL */
+    int relu2;                   /* layer 2's ReLU (after the max, which commutes with it) */
+    float* out;                  /* element (b, c, j) at out[b*out_sb + c*out_sc + j*out_sn] */
+    long long out_sb, out_sc, out_sn;
+    int B, Ns, Nt;
+} ptt_xcorr_split_desc;
+
+int ptt_xcorr_split_f32(const ptt_xcorr_split_desc* d, ptt_stream_t stream);
 /* order (B,N) i32: the points of every cloud along a Morton curve through the cloud's bounding box (flat indices b*N + n,
  * ties by index: a permutation inside each cloud), N <= 8192. Neighbours in space become neighbours in launch order. */
 int ptt_spatial_order_f32(const float* xyz, int B, int N, int32_t* order, ptt_stream_t stream);

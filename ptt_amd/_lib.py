@@ -282,6 +282,14 @@ class SaSplitDesc(Structure):
                 ("B", c_int), ("N", c_int), ("M", c_int), ("radius", c_float), ("normalize_xyz", c_int)]
 
 
+class XcorrSplitDesc(Structure):
+    """ptt_xcorr_split_desc: CosineSimAug's two 256 -> 256 layers in split-bf16 arithmetic (W1s / W2s are split-bf16 packs)."""
+    _fields_ = [("cos_t", c_void_p), ("P", c_void_p), ("w_sim", c_void_p),
+                ("W1s", c_void_p), ("shift1", c_void_p), ("W2s", c_void_p), ("shift2", c_void_p), ("relu2", c_int),
+                ("out", c_void_p), ("out_sb", c_longlong), ("out_sc", c_longlong), ("out_sn", c_longlong),
+                ("B", c_int), ("Ns", c_int), ("Nt", c_int)]
+
+
 _lib = None
 
 

@@ -14,7 +14,7 @@ LIBDIR = os.path.join(ROOT, "ptt_amd", "lib")
 LIB = os.path.join(LIBDIR, "libptt_hip.so")
 HEADER = os.path.join(ROOT, "include", "ptt_hip.h")        # the C ABI: compiled against here, bound from by _lib.py
 
-HIP_SOURCES = ["errors.hip", "point_ops.hip", "mfma_ops.hip", "track_ops.hip", "train_ops.hip", "gemm_ops.hip", "rowjobs.hip", "step_ops.hip", "wgrad_stream.hip", "pair_split.hip", "sa_split.hip"]
+HIP_SOURCES = ["errors.hip", "point_ops.hip", "mfma_ops.hip", "track_ops.hip", "train_ops.hip", "gemm_ops.hip", "rowjobs.hip", "step_ops.hip", "wgrad_stream.hip", "pair_split.hip", "sa_split.hip", "xcorr_split.hip"]
 # FPS / ball query / kNN index parity needs un-fused fp32 arithmetic (see point_ops.hip header)
 EXTRA_FLAGS = {"point_ops.hip": ["-ffp-contract=off"], "track_ops.hip": ["-ffp-contract=off"], # -fno-honor-nans: without it every fmaxf on an MFMA result costs a second v_max (sNaN canonicalisation), and
                # vector-ALU instructions next to fp32 MFMAs are paid in matrix time (a third of the epilogue instructions)
@@ -23,6 +23,7 @@ EXTRA_FLAGS = {"point_ops.hip": ["-ffp-contract=off"], "track_ops.hip": ["-ffp-c
                "rowjobs.hip": ["-fno-honor-nans"],
                "pair_split.hip": ["-fno-honor-nans"],
                "sa_split.hip": ["-fno-honor-nans"],
+               "xcorr_split.hip": ["-fno-honor-nans"],
                # accumulators in vector registers: see the file's header (one wave per SIMD otherwise)
                "wgrad_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # build-time only: flags for every source, e.g. PTT_HIP_FLAGS="-DPTT_DEV" for a developer build that reads the PTT_*

@@ -17,6 +17,18 @@ from ... import ops, train_ops
 from ...param_cache import DropsCachesOnModeChange, FoldedLayer, ParamCache, fold_conv_bn
 from ..backbones_3d.pointnet2 import pytorch_utils as layer_utils
 
+PRECISIONS = ('fp32', 'bf16x2')
+# Fewest search points (B * n2) of a batched call that precision 'bf16x2' sends to the split-bf16 kernel (ptt_xcorr_split_f32).
+# The rule is SPLIT_STREAM_MIN_BALLS' (pointnet2_modules.py): the split kernel is dispatched only where
+# scripts/xcorr_split_timing.py shows it faster than xcorr_fused_kernel<2, false> by more than the fp32 arm's own spread; a call
+# below this count runs in fp32 with a note. Measured (kernel launch alone, us, fp32 / split; fp32 arm's min - max spread in
+# brackets; Nt = 64 unless stated):
+#   points   640 (5 x 128)          1024 (8 x 128)         6144 (48 x 128)       8192 (8 x 1024, Nt = 512)
+#            111.9 / 34.5 [3.4]     152.5 / 49.0 [6.8]     798.5 / 246.2 [59]    8143 / 2415 [6.1]
+# The split kernel wins at every count by many spreads, so the threshold is 0: every batched call of the shape is dispatched
+# (DESIGN.md "Split-bf16 xcorr kernel", profiles/xcorr_split_timing.json).
+SPLIT_XCORR_MIN_POINTS = 0
+
 
 class CosineSimAug(DropsCachesOnModeChange, nn.Module):
     def __init__(self, model_cfg):
@@ -30,6 +42,52 @@ class CosineSimAug(DropsCachesOnModeChange, nn.Module):
             .conv1d(self.model_cfg.CONV.CHANNELS[2], activation=None)
         )
         self._cache = ParamCache()
+        self._split_cache = ParamCache()   # the split-bf16 packs of the two remaining layers: built only under precision 'bf16x2'
+        self._precision = 'fp32'
+        # optional PRECISION: 'fp32' (absent) or 'bf16x2', the split-bf16 kernel of the batched (template, search) pair MLP
+        self.precision = model_cfg.get('PRECISION', 'fp32') if hasattr(model_cfg, 'get') else getattr(model_cfg, 'PRECISION', 'fp32')
+
+    # ------------------------------------------------------------------ arithmetic of the batched pair MLP
+    @property
+    def precision(self):
+        """'fp32' (default) or 'bf16x2': an eval-mode call that would reach the batched fused kernel (cosine map +
+        xcorr_fused_kernel<2, false>) with C0 = 256 and two remaining layers 256 -> 256 -> 256 takes the operands of its two GEMMs
+        as two bf16 pieces each (ptt_xcorr_split_f32). Every other call — the two-workgroup one-frame form, other widths or depths,
+        training, the CPU — runs what it ran before and says so once."""
+        return getattr(self, '_precision', 'fp32')
+
+    @precision.setter
+    def precision(self, value):
+        if value not in PRECISIONS:
+            raise ValueError("CosineSimAug.precision must be one of %s, got %r" % (", ".join(map(repr, PRECISIONS)), value))
+        if value != self.precision:
+            self._cache.drop()          # a captured graph addressed the old mode's buffers
+            self._split_cache.drop()    # the split packs exist only under 'bf16x2'
+        self._precision = value
+
+    def _split_params(self):
+        """-> dict(w1s, shift1, w2s, shift2, relu2): the two remaining SharedMLP layers for ops.xcorr_split — the BatchNorm scale
+        folded into the weights in float32 (the values the fp32 pack holds), then ops.pack_weight_split."""
+        ts = list(self.state_dict().values())
+        return self._split_cache.get(ts, ts[0].device, self._fold_split)
+
+    def _fold_split(self):
+        packs = []
+        for u in list(self.mlp)[1:3]:
+            sc, sh = fold_conv_bn(u)
+            packs.append((ops.pack_weight_split(u.conv.weight * sc.view(-1, 1, 1, 1)), sh))
+        return dict(w1s=packs[0][0], shift1=packs[0][1], w2s=packs[1][0], shift2=packs[1][1], relu2=hasattr(self.mlp[2], 'activation'))
+
+    @staticmethod
+    def _split_reason(P, points):
+        """None when this batched eval-mode call runs the split-bf16 kernel, else why it stays on the fp32 kernel."""
+        L = P['layers']
+        if (P['c0'] != 256 or len(L) != 2 or (L[0].cin, L[0].cout, L[1].cin, L[1].cout) != (256, 256, 256, 256) or not L[0].relu
+                or L[0].scale is not None or L[1].scale is not None):
+            return 'other widths or depths than C0 = 256, 256 -> 256 -> 256: fp32 only'
+        if points < SPLIT_XCORR_MIN_POINTS:
+            return 'fewer than %d search points: the split-bf16 xcorr kernel is not faster there, not dispatched' % SPLIT_XCORR_MIN_POINTS
+        return None
 
     # ------------------------------------------------------------------ fused-path parameters
     def _fusable(self, search_feats, template_feats):
@@ -84,6 +142,7 @@ class CosineSimAug(DropsCachesOnModeChange, nn.Module):
         template_xyz = batch_dict['template_seeds']          # (B,n1,3)
         b, f, n2 = search_feats.shape
         n1 = template_feats.shape[-1]
+        split = self.precision == 'bf16x2'
 
         if self._fusable(search_feats, template_feats):
             P = self._params()
@@ -98,12 +157,22 @@ class CosineSimAug(DropsCachesOnModeChange, nn.Module):
                 pre = ops.linear(rows, P['w_rest'], P['c0'], P['scale0'], P['shift0'])        # (B,n1,C0), BN folded in
             if b * n2 <= ops.ONE_FRAME_MAX_POINTS:
                 # a handful of frames: two workgroups per search point, cosines formed in the kernel (one launch less)
+                if split:
+                    ops.note_precision_fallback('CosineSimAug', 'a handful of frames: the two-workgroup one-frame form is fp32 only')
                 fused, _ = ops.xcorr_fused(search_feats, template_feats, pre, P['w_sim'], None, None,
                                            P['layers'], eps=self.cosine.eps, split=True)      # (B,C,n2) view
             else:
                 cos_t = ops.cosine_map(search_feats, template_feats, eps=self.cosine.eps)     # (B,n2,n1), one launch
-                fused, _ = ops.xcorr_fused(search_feats, template_feats, pre, P['w_sim'], None, None,
-                                           P['layers'], eps=self.cosine.eps, cos_t=cos_t)     # (B,C,n2) view
+                reason = self._split_reason(P, b * n2) if split else 'fp32'
+                if reason is None:
+                    S = self._split_params()
+                    fused = ops.xcorr_split(cos_t, pre, P['w_sim'], S['w1s'], S['shift1'], S['w2s'], S['shift2'],
+                                            relu2=S['relu2'])                                 # (B,C,n2) view
+                else:
+                    if split:
+                        ops.note_precision_fallback('CosineSimAug', reason)
+                    fused, _ = ops.xcorr_fused(search_feats, template_feats, pre, P['w_sim'], None, None,
+                                               P['layers'], eps=self.cosine.eps, cos_t=cos_t) # (B,C,n2) view
             if fused.dim() == 4:
                 # the split form's two halves: their element-wise maximum (= the max over the template axis) is taken by the
                 # first trailing convolution while it stages its operand
@@ -119,6 +188,10 @@ class CosineSimAug(DropsCachesOnModeChange, nn.Module):
             batch_dict['cosine_feats'] = y.transpose(1, 2)                                    # (B,c,n2) view
             return batch_dict
 
+        if split:
+            ops.note_precision_fallback('CosineSimAug', 'training: the training forms are fp32 only' if self.training else
+                                        'CPU: no split-bf16 form' if not search_feats.is_cuda else
+                                        'the fused path turned this call away: the stock path is fp32 only')
         if (train_ops.usable(self.mlp, search_feats) and self.mlp[0].conv.weight.shape[1] == f + 4
                 and self.mlp[0].conv.weight.shape[0] % 4 == 0 and self.mlp[0].conv.weight.shape[0] <= 256):   # ptt_xcorr_z0_bwd_f32: C0 <= 256
             # training on a HIP device: layer 0 split per template point + similarity term (train_ops.xcorr_hoisted),

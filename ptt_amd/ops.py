@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, AttnSplitDesc, SaDesc, SaLayer, SaSplitDesc, XcorrDesc
+from ._lib import AttnDesc, AttnSplitDesc, SaDesc, SaLayer, SaSplitDesc, XcorrDesc, XcorrSplitDesc
 
 
 def _stream():
@@ -710,6 +710,46 @@ def xcorr_fused(search_feats, templ_feats, P, w_sim, scale0, shift0, layers, eps
     _fill_layers(d.layers, layers)
     _launch("ptt_xcorr_fused_fwd_f32", P.device, ctypes.byref(d), timed='ptt_xcorr_fused_fwd_f32')
     return out, sim
+
+
+def xcorr_split(cos_t, P, w_sim, w1s, shift1, w2s, shift2, relu2=True, out=None):
+    """The batched CosineSimAug core of xcorr_fused (cos_t given) in split-bf16 arithmetic (ptt_xcorr_split_f32), at the one shape
+    C0 = 256, 256 -> 256 (ReLU) -> 256. h0 = max(P_i + w_sim * cos_ij, 0) is formed in fp32 as there; both layers take every operand
+    as two bf16 pieces (hi.hi + hi.lo + lo.hi, fp32 accumulation); shifts, ReLUs, the max over the template points and the store
+    are fp32. cos_t (B,Ns,Nt) from cosine_map, Nt % 64 == 0; P (B,Nt,256) contiguous with layer 0's BatchNorm folded in; w_sim
+    (256), scale folded; w1s / w2s = pack_weight_split of the two (256,256) weights with the BatchNorm scale folded in; shift1 /
+    shift2 (256) float32 or None. out: an optional (B,256,Ns) float32 view to write (any non-negative strides).
+    Returns (B,256,Ns), a transposed view of (B,Ns,256) storage unless out is given."""
+    _chk(cos_t, "cos_t", torch.float32, 3)
+    _chk(P, "P", torch.float32, 3)
+    _chk(w_sim, "w_sim", torch.float32, 1)
+    B, Ns, Nt = cos_t.shape
+    if tuple(P.shape) != (B, Nt, 256) or w_sim.numel() != 256:
+        raise ValueError("xcorr_split: cos_t (B,Ns,Nt), P (B,Nt,256) and w_sim (256) expected (got cos_t %s, P %s, w_sim %s)"
+                         % (tuple(cos_t.shape), tuple(P.shape), tuple(w_sim.shape)))
+    for name, t in (("w1s", w1s), ("w2s", w2s)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int16 or t.numel() != 2 * 256 * 256 or not t.is_cuda:
+            raise ValueError("xcorr_split: %s must be pack_weight_split of a (256,256) weight" % name)
+    for name, t in (("shift1", shift1), ("shift2", shift2)):
+        if t is not None:
+            _chk(t, name, torch.float32, 1)
+            if t.numel() != 256:
+                raise ValueError("xcorr_split: %s must have 256 elements" % name)
+    if out is None:
+        out = torch.empty((B, Ns, 256), dtype=torch.float32, device=P.device).transpose(1, 2)
+    elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, 256, Ns):
+        raise ValueError("xcorr_split: out must be a (B,256,Ns) float32 device tensor")
+    d = XcorrSplitDesc()
+    d.cos_t, d.P, d.w_sim = cos_t.data_ptr(), P.data_ptr(), w_sim.data_ptr()
+    d.W1s, d.W2s = w1s.data_ptr(), w2s.data_ptr()
+    d.shift1 = shift1.data_ptr() if shift1 is not None else None
+    d.shift2 = shift2.data_ptr() if shift2 is not None else None
+    d.relu2 = int(bool(relu2))
+    d.out = out.data_ptr()
+    d.out_sb, d.out_sc, d.out_sn = out.stride()
+    d.B, d.Ns, d.Nt = B, Ns, Nt
+    _launch("ptt_xcorr_split_f32", P.device, ctypes.byref(d), timed='ptt_xcorr_split_f32')
+    return out
 
 
 def pack_delta0(weight, bias):
