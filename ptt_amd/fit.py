@@ -385,3 +385,20 @@ def from_config(cfg, train_tracklets, device, ckpt_dir, val_tracklets=None, mode
         return fit(trainer, feeder, opt['NUM_EPOCHS'], ckpt_dir, **kw)
     run.trainer, run.feeder, run.evaluator, run.start = trainer, feeder, evaluator, (it, start_epoch)
     return run
+
+
+def from_kitti(cfg, device, ckpt_dir, root=None, missing='origin', **kw):
+    """from_config on a KITTI tracking directory (cfg.DATA_CONFIG.DATA_PATH, or `root`): the training tracklets are read from the
+    files of DATA_SPLIT.train and preloaded by LIDAR_CROP_OFFSET, the validation tracklets — only when TRAIN.WITH_EVAL.ENABLE —
+    are the whole scans of DATA_SPLIT.test (datasets/kitti/kitti_scenes.kitti_tracklets). Everything else, `kw` included, is
+    from_config's. -> its run; run.train_scenes / run.val_scenes are the two KittiTrackingScenes (val_scenes None without
+    evaluation)."""
+    from .datasets.kitti import kitti_tracklets
+    names = cfg['CLASS_NAMES'] if 'CLASS_NAMES' in cfg else 'Car'
+    data_cfg = cfg['DATA_CONFIG']
+    train = kitti_tracklets(data_cfg, names, True, device, root=root, missing=missing)
+    with_eval = cfg['TRAIN']['WITH_EVAL'] if ('TRAIN' in cfg and 'WITH_EVAL' in cfg['TRAIN']) else None
+    val = kitti_tracklets(data_cfg, names, False, device, root=root, missing=missing) if with_eval and with_eval['ENABLE'] else None
+    run = from_config(cfg, train.tracklets(), device, ckpt_dir, val_tracklets=None if val is None else val.tracklets(), **kw)
+    run.train_scenes, run.val_scenes = train, val
+    return run
